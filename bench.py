@@ -7,7 +7,7 @@ recipe), 32 agents per env, 65,536 envs per GPU, default_config.yaml params
 on-device auto-reset.  One bench "step" = one FloorFieldModel.step() of every
 env = one launch of the fused HIP kernel over inputs resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 --config picks a BASELINE.json workload: 2 (default, the headline line),
@@ -20,7 +20,15 @@ learner (ffm_learner_*): its V / H tables are shared by all envs of a GPU.
 Multi-GPU: envs are sharded by global id (weak scaling, 65,536 per GPU); the
 only collective is the final reduction of counters and times (RCCL).
 
-Rank 0 prints ONE JSON line.  `roofline.achieved` = algorithmic bytes per
+A plain run does what the headline figure needs and no more: set up, burn in, warm
+up, time ONE region of exactly --steps steps, print the result line.  --full adds the
+secondary measurements: --repeats defaults to 5 timed regions (value = their median), a
+HIP-event pass and a device-to-device copy for the roofline, the fused multi-step line
+(config 2) and the CPU baseline with its bit-exact check of the GPU state.
+--dump-outputs DIR writes the state the last timed step left (what get_state() and, for
+the learners, export_table() hand a caller) as float32 / float64 DIR/<name>.npy.
+
+Rank 0 prints ONE JSON line.  With --full, `roofline.achieved` = algorithmic bytes per
 launch (2*(2A + 4*H*W + 4) per env) / mean per-launch kernel
 time measured with HIP events on the launch stream; `traffic` comes from the
 committed rocprofv3 PMC summary (profiles/) when present; `cpu_baseline` times
@@ -74,8 +82,16 @@ def parse():
                          "through every step it ran (and check them bit-exactly); beyond it a bounded sample")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = this process's CPU share (OMP_NUM_THREADS, else its affinity set)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of K steps each, back to back; value = their median (BASELINE.md 3)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of K steps each, back to back; value = their median (BASELINE.md 3); "
+                         "default 1 (--steps is the number of timed steps), 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: 5 timed regions, the HIP-event pass and the copy "
+                         "bandwidth of the roofline, the fused multi-step line, the CPU baseline and its "
+                         "bit-exact check (--no-cpu skips that one)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the state after the last timed step as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB: a fixed seeded sample of the envs where the state is larger)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--multi-step", type=int, default=50,
                     help="config 2: also time step(K) with this many steps fused per launch "
@@ -96,6 +112,7 @@ def parse():
     a.steps = a.steps if a.steps is not None else steps
     a.warmup = a.warmup if a.warmup is not None else warmup
     a.burn_in = a.burn_in if a.burn_in is not None else {2: 1000, 5: 300}.get(a.config, 0)
+    a.repeats = a.repeats if a.repeats is not None else (5 if a.full else 1)
     return a
 
 
@@ -150,33 +167,37 @@ def main():
     reps = timed_repeats(args, world, dist, torch, lambda: eng.step(args.steps, stream),
                          lambda: eng.counters(stream))
     elapsed, agent_steps = reps["elapsed"], reps["agent_steps"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, eng.get_state(stream=stream))
 
-    # Kernel time for the roofline: HIP events on the launch stream bracketing
-    # nk back-to-back launches (a separate pass, so events do not perturb
-    # `value`); per-launch event pairs would add their own gaps to each launch.
-    # nk = the window length, so the pass averages the same phases as a timed window
-    # (config 3: one episode, its in-phase reset burst included).
-    nk = min(args.steps, 2000)
-    ev0 = torch.cuda.Event(enable_timing=True)
-    ev1 = torch.cuda.Event(enable_timing=True)
-    ev0.record(stream)
-    eng.step(nk, stream)
-    ev1.record(stream)
-    torch.cuda.synchronize()
-    kern_ms = [ev0.elapsed_time(ev1) / nk]
-    # the engine's state after every single-step launch it ran (the CPU baseline replays
-    # all envs through the same steps and compares them bit for bit)
-    single_steps = args.burn_in + args.warmup + reps["summary"]["n"] * args.steps + nk
-    snap = eng.get_state() if rank == 0 and world == 1 and not args.no_cpu else None
+    kern_ms = copy_gbs = snap = single_steps = None
+    if args.full:
+        # Kernel time for the roofline: HIP events on the launch stream bracketing
+        # nk back-to-back launches (a separate pass, so events do not perturb
+        # `value`); per-launch event pairs would add their own gaps to each launch.
+        # nk = the window length, so the pass averages the same phases as a timed window
+        # (config 3: one episode, its in-phase reset burst included).
+        nk = min(args.steps, 2000)
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev0.record(stream)
+        eng.step(nk, stream)
+        ev1.record(stream)
+        torch.cuda.synchronize()
+        kern_ms = [ev0.elapsed_time(ev1) / nk]
+        # the engine's state after every single-step launch it ran (the CPU baseline replays
+        # all envs through the same steps and compares them bit for bit)
+        single_steps = args.burn_in + args.warmup + reps["summary"]["n"] * args.steps + nk
+        snap = eng.get_state() if rank == 0 and world == 1 and not args.no_cpu else None
 
-    # Achievable HBM bandwidth on this box: a device-to-device copy of the same
-    # number of bytes one launch moves (read + write), for context beside `peak`.
-    copy_gbs = copy_bandwidth(torch, stream, E * (2 * A + 4 * H * W + 4))
+        # Achievable HBM bandwidth on this box: a device-to-device copy of the same
+        # number of bytes one launch moves (read + write), for context beside `peak`.
+        copy_gbs = copy_bandwidth(torch, stream, E * (2 * A + 4 * H * W + 4))
 
     # Secondary line: the same steps with K fused per launch (state on chip between
     # the K steps of an env pair; bit-identical results, tests/test_gpu_parity.py).
     multi = None
-    if args.multi_step > 1 and args.config == 2:
+    if args.full and args.multi_step > 1 and args.config == 2:
         eng.set_fused_steps(args.multi_step)
         eng.step(args.multi_step, stream)
         torch.cuda.synchronize()
@@ -192,26 +213,6 @@ def main():
 
     if rank == 0:
         bytes_per_env_step = 2 * (2 * A + 4 * H * W + 4)
-        mean_kernel_s = float(np.mean(kern_ms)) / 1e3
-        achieved = E * bytes_per_env_step / mean_kernel_s / 1e9
-        traffic = traffic_src = None
-        tpath = args.traffic_json or os.path.join(ROOT, "profiles", f"traffic_{H}x{W}_A{A}_E{E}.json")
-        neumann = args.neighborhood == "neumann"      # the committed profiles are the Neumann configs'
-        if os.path.exists(tpath) and (neumann or args.traffic_json):
-            with open(tpath) as f:
-                tj = json.load(f)
-            if tj.get("config") == f"{H}x{W}_A{A}_E{E}":
-                traffic = tj.get("hbm_bytes_per_launch")
-                traffic_src = profile_source(tpath, tj)
-        # the step kernel's VALU issue fraction (its real bound at 12x12) from a committed
-        # PMC summary (tools/pmc.sh + tools/valu_json.py)
-        valu = None
-        vpath = os.path.join(ROOT, "profiles", f"valu_{H}x{W}_A{A}_E{E}.json")
-        if os.path.exists(vpath) and neumann:
-            with open(vpath) as f:
-                vj = json.load(f)
-            if vj.get("config") == f"{H}x{W}_A{A}_E{E}":
-                valu = vj
         out = {
             "metric": METRIC,
             "value": agent_steps / elapsed,
@@ -243,31 +244,59 @@ def main():
             "env_steps_per_s": E * world * args.steps / elapsed,
             "mean_live_agents_per_env_step": agent_steps / (E * world * args.steps),
             "repeats": reps["summary"],
-            "kernel_ms_mean": float(np.mean(kern_ms)),
-            "kernel_ms_median": float(np.median(kern_ms)),
-            "roofline": {
-                "bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                "frac": achieved / PEAK_HBM_GBS, "traffic": traffic,
-                "traffic_source": traffic_src,
-                "bytes_per_launch_algorithmic": E * bytes_per_env_step,
-                # BASELINE.md 3's form: env-steps/s of the timed windows (launch gaps included) x B
-                "frac_env_rate": E * world * args.steps / elapsed * bytes_per_env_step / 1e9 / world / PEAK_HBM_GBS,
-                "achievable_copy_GBs": copy_gbs,
-                "frac_of_copy": achieved / copy_gbs if copy_gbs else None,
-                **({"valu_issue_frac": valu["valu_issue_frac"], "valu_per_wave": valu["valu_per_wave"],
-                    "valu_source": profile_source(os.path.join(ROOT, "profiles", f"valu_{H}x{W}_A{A}_E{E}.json"),
-                                                  valu) + f"; {valu['formula']}",
-                    "valu_calibration": VALU_CALIBRATION} if valu else {}),
-            },
-            "cpu_baseline": None,
-            "multi_step": multi,
         }
-        if not args.no_cpu and world == 1:     # the CPU baseline is an N = 1 measurement
-            out["cpu_baseline"] = cpu_baseline(args, m, s, params, snap, single_steps)
+        if args.full:
+            out.update(core_kernel_roofline(args, H, W, A, E, world, elapsed, bytes_per_env_step, kern_ms, copy_gbs))
+            out["cpu_baseline"] = None
+            out["multi_step"] = multi
+            if not args.no_cpu and world == 1:     # the CPU baseline is an N = 1 measurement
+                out["cpu_baseline"] = cpu_baseline(args, m, s, params, snap, single_steps)
         print(json.dumps(out), flush=True)
     eng.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def core_kernel_roofline(args, H, W, A, E, world, elapsed, bytes_per_env_step, kern_ms, copy_gbs):
+    """--full, configs 2/3: the event-timed kernel and the roofline fields derived from it."""
+    mean_kernel_s = float(np.mean(kern_ms)) / 1e3
+    achieved = E * bytes_per_env_step / mean_kernel_s / 1e9
+    traffic = traffic_src = None
+    tpath = args.traffic_json or os.path.join(ROOT, "profiles", f"traffic_{H}x{W}_A{A}_E{E}.json")
+    neumann = args.neighborhood == "neumann"      # the committed profiles are the Neumann configs'
+    if os.path.exists(tpath) and (neumann or args.traffic_json):
+        with open(tpath) as f:
+            tj = json.load(f)
+        if tj.get("config") == f"{H}x{W}_A{A}_E{E}":
+            traffic = tj.get("hbm_bytes_per_launch")
+            traffic_src = profile_source(tpath, tj)
+    # the step kernel's VALU issue fraction (its real bound at 12x12) from a committed
+    # PMC summary (tools/pmc.sh + tools/valu_json.py)
+    valu = None
+    vpath = os.path.join(ROOT, "profiles", f"valu_{H}x{W}_A{A}_E{E}.json")
+    if os.path.exists(vpath) and neumann:
+        with open(vpath) as f:
+            vj = json.load(f)
+        if vj.get("config") == f"{H}x{W}_A{A}_E{E}":
+            valu = vj
+    return {
+        "kernel_ms_mean": float(np.mean(kern_ms)),
+        "kernel_ms_median": float(np.median(kern_ms)),
+        "roofline": {
+            "bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+            "frac": achieved / PEAK_HBM_GBS, "traffic": traffic,
+            "traffic_source": traffic_src,
+            "bytes_per_launch_algorithmic": E * bytes_per_env_step,
+            # BASELINE.md 3's form: env-steps/s of the timed windows (launch gaps included) x B
+            "frac_env_rate": E * world * args.steps / elapsed * bytes_per_env_step / 1e9 / world / PEAK_HBM_GBS,
+            "achievable_copy_GBs": copy_gbs,
+            "frac_of_copy": achieved / copy_gbs if copy_gbs else None,
+            **({"valu_issue_frac": valu["valu_issue_frac"], "valu_per_wave": valu["valu_per_wave"],
+                "valu_source": profile_source(os.path.join(ROOT, "profiles", f"valu_{H}x{W}_A{A}_E{E}.json"),
+                                              valu) + f"; {valu['formula']}",
+                "valu_calibration": VALU_CALIBRATION} if valu else {}),
+        },
+    }
 
 
 # run_actor_only_training.py:47-58 (epsilon = EPSILON_START, :40) and
@@ -294,6 +323,47 @@ def profile_source(path, d):
     rel = os.path.relpath(path, ROOT)
     when = d.get("measured", "an earlier round")
     return f"committed profile {rel} (measured {when}; not measured in this run)"
+
+
+DUMP_STATE_BYTES = 48_000_000     # --dump-outputs: env state, then the learner tables; 60 MB in all
+DUMP_TABLE_BYTES = 12_000_000
+
+
+def dump_outputs(out_dir, rank, world, state, tables=None):
+    """--dump-outputs: what the timed path left after its last step, as float32 / float64 .npy.
+
+    `state` is get_state()'s (positions, counts, dff); the position slots past an env's count
+    are not part of the result and are written as -1.  `tables` maps "V" / "H" to
+    export_table()'s (keys, values): rows sorted by key (the insertion order is not part of
+    the result), the 64-bit keys as two exact float64 halves.  Whatever exceeds its byte budget
+    is cut to a fixed sample (Generator seeded 0) of whole envs / whole table rows, whose
+    indices are written beside it, so two builds given the same arguments dump the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+
+    def sample(n, row_bytes, budget):
+        k = min(n, max(1, budget // max(1, row_bytes)))
+        return np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+
+    pos, cnt, dff = state
+    idx = sample(len(cnt), 4 * (pos.shape[1] + 1 + dff[0].size) + 8, DUMP_STATE_BYTES)
+    p = pos[idx].astype(np.float32)
+    p[np.arange(pos.shape[1])[None, :] >= cnt[idx][:, None]] = -1.0
+    save("env_index", idx.astype(np.float64))
+    save("positions", p)
+    save("counts", cnt[idx].astype(np.float32))
+    save("dff", np.ascontiguousarray(dff[idx], dtype=np.float32))
+    for w, (keys, vals) in (tables or {}).items():
+        order = np.argsort(keys, kind="stable")
+        keys, vals = keys[order], np.asarray(vals, np.float64).reshape(len(keys), -1)[order]
+        idx = sample(len(keys), 8 * (3 + vals.shape[1]), DUMP_TABLE_BYTES // len(tables))
+        save(f"{w}_row_index", idx.astype(np.float64))
+        save(f"{w}_keys_hi", (keys[idx] >> np.uint64(32)).astype(np.float64))
+        save(f"{w}_keys_lo", (keys[idx] & np.uint64(0xFFFFFFFF)).astype(np.float64))
+        save(f"{w}_values", vals[idx])
 
 
 def timed_repeats(args, world, dist, torch, run_k, counters):
@@ -396,32 +466,27 @@ def bench_learner(args, world, rank, torch, dist):
     recv_timed = (getattr(sync, "received_bytes", 0) - recv0) if world > 1 else 0
     elapsed, agent_steps = reps["elapsed"], reps["agent_steps"]
     print(f"[bench] timed regions {reps['summary']['elapsed_s']} s", file=sys.stderr, flush=True)
-    # the event pass spans a whole timed window (config 5: one episode, its lockstep
-    # truncation and reset included), so the roofline averages what `value` averages
-    nk = min(args.steps, 300)
-    ev0 = torch.cuda.Event(enable_timing=True)
-    ev1 = torch.cuda.Event(enable_timing=True)
-    ev0.record(stream)
-    run(nk)
-    ev1.record(stream)
-    torch.cuda.synchronize()
-    step_ms = ev0.elapsed_time(ev1) / nk
+    if args.dump_outputs:
+        tabs = {}
+        if world == 1:     # (sharded runs: the ranks' tables are merged lazily, only the env state is dumped)
+            tabs = {w: L.export_table(w, stream) for w in ("V", "H") if L.table_size(w, stream)}
+        dump_outputs(args.dump_outputs, rank, world, L.get_state(stream=stream), tabs)
+    step_ms = None
+    if args.full:
+        # the event pass spans a whole timed window (config 5: one episode, its lockstep
+        # truncation and reset included), so the roofline averages what `value` averages
+        nk = min(args.steps, 300)
+        ev0 = torch.cuda.Event(enable_timing=True)
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev0.record(stream)
+        run(nk)
+        ev1.record(stream)
+        torch.cuda.synchronize()
+        step_ms = ev0.elapsed_time(ev1) / nk
     if world > 1:
         sync.flush()       # the ranks' key sets merged (the owner exchange keeps V's lazily)
     v_size, h_size = L.table_size("V"), L.table_size("H")
     if rank == 0:
-        D = 4 if cfg["variant"] == "actor_only" else 1
-        bpe = learner_bytes_per_env_step(H, W, A, D, 9 if args.neighborhood == "moore" else 5)
-        achieved = E * bpe / (step_ms / 1e3) / 1e9
-        # PMC HBM bytes of the batch kernel (tools/traffic.sh <out> --config 4|5)
-        traffic = traffic_src = None
-        tpath = os.path.join(ROOT, "profiles", f"traffic_{H}x{W}_A{A}_E{E}_learn{args.config}.json")
-        if os.path.exists(tpath) and args.neighborhood == "neumann":     # (profiled on the Neumann configs)
-            with open(tpath) as f:
-                tj = json.load(f)
-            if tj.get("config") == f"{H}x{W}_A{A}_E{E}_learn{args.config}":
-                traffic = tj.get("hbm_bytes_per_launch")
-                traffic_src = profile_source(tpath, tj)
         out = {
             "metric": METRIC, "value": agent_steps / elapsed, "unit": "agent-steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -446,7 +511,6 @@ def bench_learner(args, world, rank, torch, dist):
             "env_steps_per_s": E * world * args.steps / elapsed,
             "mean_live_agents_per_env_step": agent_steps / (E * world * args.steps),
             "repeats": reps["summary"],
-            "step_ms_events": step_ms,
             "tables": {"V": v_size, "H": h_size},
             "table_sync": (dict({"period": args.sync_period,
                                  "mode": ("owner-sharded tiles: records all-to-all, updates all-gathered"
@@ -461,22 +525,43 @@ def bench_learner(args, world, rank, torch, dist):
                                 **({} if sync.dense or sync.tiled else {"record_capacity": dict(sync.caps),
                                                           "max_touched_records": dict(sync.max_count)}))
                            if world > 1 else {"period": args.sync_period}),
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                         "frac": achieved / PEAK_HBM_GBS, "traffic": traffic,
-                         "traffic_kernel": "learn_batch_kernel (PMC FETCH_SIZE x2 + WRITE_SIZE)",
-                         "traffic_source": traffic_src,
-                         "bytes_per_launch_algorithmic": E * bpe,
-                         # BASELINE.md 3's form: env-steps/s of the timed windows x the bytes per env-step
-                         "frac_env_rate": E * args.steps / elapsed * bpe / 1e9 / PEAK_HBM_GBS,
-                         "note": "whole learning step (all kernels) timed with HIP events"},
-            "cpu_baseline": None,
         }
-        if not args.no_cpu and world == 1:
-            out["cpu_baseline"] = cpu_baseline_learner(args, cfg, m, s)
+        if args.full:
+            out.update(learner_step_roofline(args, cfg, H, W, A, E, elapsed, step_ms))
+            out["cpu_baseline"] = None
+            if not args.no_cpu and world == 1:
+                out["cpu_baseline"] = cpu_baseline_learner(args, cfg, m, s)
         print(json.dumps(out), flush=True)
     L.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def learner_step_roofline(args, cfg, H, W, A, E, elapsed, step_ms):
+    """--full, configs 4/5: the event-timed learning step and the roofline fields derived from it."""
+    D = 4 if cfg["variant"] == "actor_only" else 1
+    bpe = learner_bytes_per_env_step(H, W, A, D, 9 if args.neighborhood == "moore" else 5)
+    achieved = E * bpe / (step_ms / 1e3) / 1e9
+    # PMC HBM bytes of the batch kernel (tools/traffic.sh <out> --config 4|5)
+    traffic = traffic_src = None
+    tpath = os.path.join(ROOT, "profiles", f"traffic_{H}x{W}_A{A}_E{E}_learn{args.config}.json")
+    if os.path.exists(tpath) and args.neighborhood == "neumann":     # (profiled on the Neumann configs)
+        with open(tpath) as f:
+            tj = json.load(f)
+        if tj.get("config") == f"{H}x{W}_A{A}_E{E}_learn{args.config}":
+            traffic = tj.get("hbm_bytes_per_launch")
+            traffic_src = profile_source(tpath, tj)
+    return {
+        "step_ms_events": step_ms,
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                     "frac": achieved / PEAK_HBM_GBS, "traffic": traffic,
+                     "traffic_kernel": "learn_batch_kernel (PMC FETCH_SIZE x2 + WRITE_SIZE)",
+                     "traffic_source": traffic_src,
+                     "bytes_per_launch_algorithmic": E * bpe,
+                     # BASELINE.md 3's form: env-steps/s of the timed windows x the bytes per env-step
+                     "frac_env_rate": E * args.steps / elapsed * bpe / 1e9 / PEAK_HBM_GBS,
+                     "note": "whole learning step (all kernels) timed with HIP events"},
+    }
 
 
 def cpu_baseline_learner(args, cfg, m, s):

@@ -655,3 +655,51 @@ def test_engine_trajectory_capture_stops_when_empty_without_auto_reset():
         assert k == 0 and st == list(range(1, len(st) + 1))
         assert len(ps[-1]) == 0 and all(len(q) > 0 for q in ps[:-1])
     eng.close()
+
+
+# ---------------------------------------------------------------------------
+# bench.py: the plain and --full result lines, --steps, --dump-outputs
+# ---------------------------------------------------------------------------
+def _bench_line(monkeypatch, capsys, *argv):
+    import json
+
+    import bench
+    monkeypatch.setattr("sys.argv", ["bench.py", *argv])
+    bench.main()
+    return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+
+
+def test_bench_plain_run_times_steps_once_and_dumps_the_last_state(monkeypatch, capsys, tmp_path):
+    """A plain run is one timed region with none of --full's fields, and it runs exactly --steps
+    timed steps: --dump-outputs holds, bit for bit, the state a fresh engine has after
+    burn-in + warmup + steps steps."""
+    from ffm_amd.data import make_room, l1_sff
+    small = ("--gpus", "1", "--envs", "300", "--burn-in", "7", "--warmup", "2", "--steps", "5")
+    d = _bench_line(monkeypatch, capsys, *small, "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["repeats"]["n"] == 1
+    assert d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "agent-steps/s" and d["higher_is_better"] is True
+    # (elapsed_s is rounded to the microsecond: 0.5e-6 s / 5 steps = 1e-4 ms)
+    assert abs(d["ms_per_step"] - d["repeats"]["elapsed_s"][0] / 5 * 1e3) <= 1.01e-4
+    assert not {"roofline", "cpu_baseline", "multi_step", "kernel_ms_mean"} & d.keys()
+    m = make_room(12, 12)
+    eng = _engine(map_array=m, sff=l1_sff(m), n_envs=300, n_agents=32, rng="philox", seed=42, auto_reset=True,
+                  params={"k_S": 3, "k_D": 1, "diffuse": 0.2, "decay": 0.2, "neighborhood": "neumann"})
+    eng.reset()
+    eng.step(7 + 2 + 5)
+    pos, cnt, dff = eng.get_state()
+    eng.close()
+    got = {f.name[:-4]: np.load(f) for f in tmp_path.iterdir()}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["env_index"], np.arange(300)) and np.array_equal(got["counts"], cnt)
+    assert np.array_equal(got["dff"].view(np.uint32), dff.view(np.uint32))
+    live = np.arange(32)[None, :] < cnt[:, None]
+    assert np.array_equal(got["positions"][live], pos[live]) and np.all(got["positions"][~live] == -1)
+
+
+def test_bench_full_run_keeps_the_secondary_fields(monkeypatch, capsys):
+    d = _bench_line(monkeypatch, capsys, "--gpus", "1", "--envs", "300", "--burn-in", "7", "--warmup", "2",
+                    "--steps", "5", "--full", "--multi-step", "5", "--cpu-budget", "30")
+    assert d["repeats"]["n"] == 5 and d["steps"] == 5
+    assert d["kernel_ms_mean"] > 0 and d["roofline"]["achieved"] > 0 and d["roofline"]["achievable_copy_GBs"] > 0
+    assert d["multi_step"]["fused_steps"] == 5 and d["multi_step"]["value"] > 0
+    assert d["cpu_baseline"]["bit_exact_vs_gpu"] is True and d["cpu_baseline"]["checked_envs"] == 300

@@ -36,3 +36,45 @@ def test_rank_key_roundtrip():
     assert K.to_rank_tuple(K.from_rank_tuple(k)) == k
     b = pickle.dumps(k)
     assert K.to_rank_tuple(K.from_rank_tuple(pickle.loads(b))) == k
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_fixed_samples(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 files only, dead position slots as -1, table
+    rows sorted by key with exact key halves, and the same seeded sample on every call once
+    the state or a table exceeds its byte budget."""
+    import bench
+    rng = np.random.default_rng(3)
+    E, A, H, W = 40, 6, 5, 7
+    pos = rng.integers(0, H * W, (E, A)).astype(np.uint16)
+    cnt = rng.integers(0, A + 1, E).astype(np.int32)
+    dff = rng.random((E, H, W), dtype=np.float32)
+    keys = rng.permutation(np.arange(1, 31, dtype=np.uint64) * np.uint64(0x1_0000_0003))
+    hv = rng.random((30, 5))
+    tabs = {"V": (keys, hv[:, 0].copy()), "H": (keys, hv)}
+
+    def load(d):
+        out = {f.name[:-4]: np.load(f) for f in d.iterdir()}
+        assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+        return out
+
+    bench.dump_outputs(str(tmp_path / "all"), 0, 1, (pos, cnt, dff), tabs)
+    d = load(tmp_path / "all")
+    assert np.array_equal(d["env_index"], np.arange(E))
+    assert np.array_equal(d["counts"], cnt) and np.array_equal(d["dff"], dff)
+    live = np.arange(A)[None, :] < cnt[:, None]
+    assert np.array_equal(d["positions"][live], pos[live]) and np.all(d["positions"][~live] == -1)
+    order = np.argsort(keys)
+    got = d["H_keys_hi"].astype(np.uint64) << np.uint64(32) | d["H_keys_lo"].astype(np.uint64)
+    assert np.array_equal(got, keys[order]) and np.array_equal(d["H_values"], hv[order])
+    assert d["V_values"].shape == (30, 1) and np.array_equal(d["V_values"][:, 0], hv[order, 0])
+
+    monkeypatch.setattr(bench, "DUMP_STATE_BYTES", 10 * (4 * (A + 1 + H * W) + 8))
+    monkeypatch.setattr(bench, "DUMP_TABLE_BYTES", 2 * 7 * 8 * (3 + 5))
+    bench.dump_outputs(str(tmp_path / "a"), 0, 1, (pos, cnt, dff), tabs)
+    bench.dump_outputs(str(tmp_path / "b"), 0, 1, (pos, cnt, dff), tabs)
+    a, b = load(tmp_path / "a"), load(tmp_path / "b")
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    idx = a["env_index"].astype(int)
+    assert len(idx) == 10 and np.all(np.diff(idx) > 0) and np.array_equal(a["dff"], dff[idx])
+    rows = a["H_row_index"].astype(int)
+    assert len(rows) == 7 and np.array_equal(a["H_values"], hv[order][rows])

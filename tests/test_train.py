@@ -5,7 +5,7 @@ run_critic_training.py's, ``--variant unified`` run_unified_*_training.py's -- a
 each is what main() hands the Learner."""
 from __future__ import annotations
 
-import ast
+import json
 import os
 
 import numpy as np
@@ -13,27 +13,14 @@ import pytest
 
 from ffm_amd import train as T
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_driver_constants.json")
 
 
 def _ref_constants(script):
-    """Module-level constants of a reference driver, read as text (never imported)."""
-    path = os.path.join(REF, script)
-    if not os.path.exists(path):
-        pytest.skip("reference checkout absent")
-    tree = ast.parse(open(path, encoding="utf-8").read())
-    out = {}
-    for node in tree.body:
-        if isinstance(node, ast.Assign) and len(node.targets) == 1 and isinstance(node.targets[0], ast.Name):
-            try:
-                out[node.targets[0].id] = ast.literal_eval(node.value)
-            except ValueError:
-                if isinstance(node.value, ast.Dict):      # MODEL_PARAMS references EPSILON_START
-                    d = {}
-                    for k, v in zip(node.value.keys, node.value.values):
-                        d[ast.literal_eval(k)] = (out[v.id] if isinstance(v, ast.Name) else ast.literal_eval(v))
-                    out[node.targets[0].id] = d
-    return out
+    """Module-level constants of a reference driver, as tests/golden/gen_driver_constants.py
+    recorded them from the driver's text."""
+    with open(GOLDEN, encoding="utf-8") as f:
+        return json.load(f)[script]
 
 
 @pytest.mark.parametrize("variant,script", [("actor_only", "run_actor_only_training.py"),

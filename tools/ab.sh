@@ -10,7 +10,7 @@ pick='import json,sys; d=json.loads(sys.stdin.read()); r=d["repeats"]; print(rou
 for r in 1 2 3; do
   for f in $LIBS; do
     lib=${f%%@*}; kv=""; [ "$lib" != "$f" ] && kv=${f#*@}
-    v=$(env $kv FFM_LIB_PATH=$PWD/$lib timeout -k 10 120 python3 bench.py --no-cpu "$@" 2>/dev/null | python3 -c "$pick") || exit 1
+    v=$(env $kv FFM_LIB_PATH=$PWD/$lib timeout -k 10 120 python3 bench.py --full --no-cpu "$@" 2>/dev/null | python3 -c "$pick") || exit 1
     echo "$(basename $lib .so)${kv:+[$kv]} $v"
   done
 done

@@ -9,10 +9,10 @@ pick='import json,sys; d=json.loads(sys.stdin.read()); print(round(d.get("step_m
 for r in 1 2 3; do
   v=$( (cd build_ab/base_tree && timeout -k 10 180 python3 bench.py --no-cpu $ARGS 2>/dev/null) | python3 -c "$pick") || exit 1
   echo "base $v"
-  v=$(timeout -k 10 180 python3 bench.py --no-cpu --burn-in 0 $ARGS 2>/dev/null | python3 -c "$pick") || exit 1
+  v=$(timeout -k 10 180 python3 bench.py --full --no-cpu --burn-in 0 $ARGS 2>/dev/null | python3 -c "$pick") || exit 1
   echo "cur $v"
   for kv in "$@"; do
-    v=$(env $kv timeout -k 10 180 python3 bench.py --no-cpu --burn-in 0 $ARGS 2>/dev/null | python3 -c "$pick") || exit 1
+    v=$(env $kv timeout -k 10 180 python3 bench.py --full --no-cpu --burn-in 0 $ARGS 2>/dev/null | python3 -c "$pick") || exit 1
     echo "cur[$kv] $v"
   done
 done

@@ -12,10 +12,10 @@ pick='import json,sys; d=json.loads(sys.stdin.read()); print(round(d.get("step_m
 for r in 1 2 3; do
   for lib in lad/libffm_amd_lad0.so lad/libffm_amd_lad1.so lad/libffm_amd_lad2.so lad/libffm_amd_lad3.so; do
     for n in 17 32; do
-      v=$(FFM_LIB_PATH=$PWD/$lib timeout -k 10 120 python3 bench.py --no-cpu --agents $n --burn-in 0 --steps 500 --warmup 20 "$@" 2>>"$OUT/err.log" | python3 -c "$pick") || exit 1
+      v=$(FFM_LIB_PATH=$PWD/$lib timeout -k 10 120 python3 bench.py --full --no-cpu --agents $n --burn-in 0 --steps 500 --warmup 20 "$@" 2>>"$OUT/err.log" | python3 -c "$pick") || exit 1
       echo "$(basename $lib .so) agents=$n $v"
     done
   done
-  v=$(timeout -k 10 120 python3 bench.py --no-cpu --steps 500 --warmup 20 "$@" 2>>"$OUT/err.log" | python3 -c "$pick") || exit 1
+  v=$(timeout -k 10 120 python3 bench.py --full --no-cpu --steps 500 --warmup 20 "$@" 2>>"$OUT/err.log" | python3 -c "$pick") || exit 1
   echo "product agents=32 $v"
 done

@@ -7,7 +7,7 @@ set -o pipefail
 OUT=gpurun_out/${1:-lp}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 400 python3 bench.py --config 3 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err" || { echo "bench c3 failed"; tail -20 "$OUT/bench_c3.err"; exit 1; }
+timeout -k 10 400 python3 bench.py --full --config 3 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err" || { echo "bench c3 failed"; tail -20 "$OUT/bench_c3.err"; exit 1; }
 tail -1 "$OUT/bench_c3.json" | cut -c1-600
 for c in 4 5; do
   timeout -k 10 600 bash tools/traffic.sh "$OUT/traffic_c$c" --config $c || { echo "traffic c$c failed"; exit 1; }

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 timeout -k 10 600 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -v --timeout 120 --timeout-method thread ${K:+-k "$K"} > "$OUT/pytest.log" 2>&1 || { echo "pytest failed"; tail -30 "$OUT/pytest.log"; exit 1; }
 tail -2 "$OUT/pytest.log"
 for epb in 0 -1; do
-  timeout -k 10 300 python bench.py --no-cpu --envs-per-block $epb > "$OUT/bench_epb$epb.json" 2> "$OUT/bench_epb$epb.err" || { echo "bench $epb failed"; tail -20 "$OUT/bench_epb$epb.err"; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu --envs-per-block $epb > "$OUT/bench_epb$epb.json" 2> "$OUT/bench_epb$epb.err" || { echo "bench $epb failed"; tail -20 "$OUT/bench_epb$epb.err"; exit 1; }
   python -c "import json;d=json.load(open('$OUT/bench_epb$epb.json'));print('epb $epb', round(d['value']/1e9,2),'G', round(d['kernel_ms_mean']*1e3,2),'us', d['repeats']['values'])"
 done
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 bench.py --no-cpu --steps 200 --warmup 20 --repeats 1 > "$OUT/trace.log" 2>&1 || { echo "trace failed"; exit 1; }
