@@ -237,7 +237,11 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
     // pos / cnt / DFF hold whole groups of 8 envs (zeroed padding beyond n_envs): the group kernel
     // reads and writes a partial last group through whole-array buffer resources (core_group.hip)
     const size_t Ep = (E + 7) & ~(size_t)7;
-    ALLOC(e->d_pos, Ep * A * 2 + 16);   // + a dword: the lane kernel streams positions as dwords
+    // + a tail pad: the lane kernel streams positions as dwords, and the group kernel's position
+    // load spans G * 64 bytes from its group's base whatever A is (a group holds G * A * 2), so
+    // with few agents the last group's load reaches past Ep * A * 2 -- by at most 8 * 64 bytes
+    const size_t pos_bytes = Ep * A * 2 + 512;
+    ALLOC(e->d_pos, pos_bytes);
     ALLOC(e->d_cnt, Ep * 4);
     ALLOC(e->d_dff, Ep * HW * 4);
     ALLOC(e->d_eps, E * 4);
@@ -278,6 +282,10 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
             const int per_cu = std::max(1, ffm::core_multi_blocks_per_cu(a, d.neighborhood));
             const long long pairs = (d.n_envs + 1) / 2;
             e->multi_blocks = (int)std::max<long long>(1, std::min<long long>((pairs + 3) / 4, (long long)cus * per_cu));
+            if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {   // diagnostic override of the grid
+                const long long v = std::atoll(ov);
+                if (v > 0) e->multi_blocks = (int)std::min<long long>(v, (pairs + 3) / 4);
+            }
         }
         if (e->group) {
             e->group_g = ffm::core_group_pick_envs(a, d.neighborhood, d.n_envs, cus);
@@ -325,7 +333,7 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
         for (size_t i = 0; i < fl.size(); i++) fp[i] = (uint16_t)((fl[i] / W + 1) * PW + fl[i] % W + 1);
         he = hipMemcpy(e->d_free_padded, fp.data(), fp.size() * 2, hipMemcpyHostToDevice);
     }
-    if (he == hipSuccess) he = hipMemset(e->d_pos, 0xFF, Ep * A * 2);
+    if (he == hipSuccess) he = hipMemset(e->d_pos, 0xFF, pos_bytes);
     if (he == hipSuccess) he = hipMemset(e->d_cnt, 0, Ep * 4);
     if (he == hipSuccess) he = hipMemset(e->d_dff, 0, Ep * HW * 4);
     if (he == hipSuccess) he = hipMemset(e->d_eps, 0, E * 4);
@@ -666,6 +674,31 @@ int ffm_engine_set_step_index(ffm_engine* e, uint32_t t) {
 int ffm_debug_read(ffm_engine* e, uint64_t* out, int n) {
     if (!e || !out || n < 0 || n > 16) return fail(FFM_E_INVALID, "bad args");
     HIP_TRY(hipMemcpy(out, e->d_dbg, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return FFM_OK;
+}
+
+// Diagnostic (not part of the ABI header): the launch geometry chosen at create.
+//   out[0] step kernel (0 group, 1 lane, 2 wave, 3 block, 4 block with global scratch)
+//   out[1] envs per group of the group kernel (0 for the other kernels)
+//   out[2] blocks of the step kernel's grid
+//   out[3] K, envs per workgroup of the block kernel
+//   out[4] threads per block of the step kernel
+//   out[5] 1 if the fused multi-step kernel is available, out[6] its grid's blocks
+int ffm_debug_launch_info(ffm_engine* e, int32_t* out, int n) {
+    if (!e || !out || n < 0 || n > 7) return fail(FFM_E_INVALID, "bad args");
+    const int kernel = e->group ? 0 : e->lane ? 1 : e->wave ? 2 : e->big ? 4 : 3;
+    const long long E = e->d.n_envs;
+    const int32_t v[7] = {
+        kernel,
+        e->group ? e->group_g : 0,
+        e->group ? e->group_blocks : e->lane ? e->lane_blocks : e->wave ? e->wave_blocks
+                                                                        : (int32_t)((E + e->K - 1) / e->K),
+        e->K,
+        kernel <= 2 ? 256 : e->big ? 1024 : e->block,
+        e->multi ? 1 : 0,
+        e->multi ? e->multi_blocks : 0,
+    };
+    for (int i = 0; i < n; i++) out[i] = v[i];
     return FFM_OK;
 }
 

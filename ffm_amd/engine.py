@@ -133,6 +133,8 @@ def load_library():
     L.ffm_engine_set_trajectory_capture.argtypes = [P, P, P, i32, i32, i64, P]
     L.ffm_engine_drain_trajectory.argtypes = [P, P, P, i64, C.POINTER(i64), C.POINTER(i64), P]
     L.ffm_np_expf_device.argtypes = [P, P, i64, P]
+    L.ffm_debug_launch_info.argtypes = [P, P, C.c_int]   # diagnostic, not in the ABI header
+    L.ffm_debug_launch_info.restype = C.c_int
     L.ffm_learner_create.argtypes = [C.POINTER(EngineDesc), C.POINTER(LearnDesc), C.POINTER(P)]
     L.ffm_learner_destroy.argtypes = [P]
     L.ffm_learner_reset.argtypes = [P, P]
@@ -458,6 +460,17 @@ class Engine:
         b = DeviceBuffers()
         _check(self._L.ffm_engine_device_buffers(self._h, C.byref(b)))
         return {k: b.__getattribute__(k) for k, _ in DeviceBuffers._fields_}
+
+    def launch_info(self) -> dict:
+        """The launch geometry chosen at create (diagnostic, ffm_debug_launch_info): the step
+        kernel ("group", "lane", "wave", "block" or "block_scratch"), the group kernel's envs per
+        group (0 for the other kernels), the step grid's blocks, the block kernel's envs per
+        workgroup K, the block size, and the fused multi-step kernel's availability and grid."""
+        v = np.zeros(7, np.int32)
+        _check(self._L.ffm_debug_launch_info(self._h, _ptr(v), len(v)))
+        return {"kernel": ("group", "lane", "wave", "block", "block_scratch")[int(v[0])], "group_g": int(v[1]),
+                "blocks": int(v[2]), "K": int(v[3]), "block_size": int(v[4]), "multi": bool(v[5]),
+                "multi_blocks": int(v[6])}
 
     @property
     def step_index(self) -> int:

@@ -5,7 +5,7 @@ import random
 import numpy as np
 import pytest
 
-from golden_util import case_names, dff_hash, load_case
+from golden_util import case_names, dff_hash, inject_names, load_case, load_inject, np_expf_tail_inputs
 from oracle import oracle as O
 
 CASES = case_names()
@@ -33,6 +33,33 @@ def test_oracle_matches_reference_goldens(name):
                 assert np.array_equal(dff.view(np.uint32), ep.full[t].view(np.uint32))
         assert [O.lib().ffo_mt_next(np_rng) for _ in range(4)] == list(ep.np_tail), "np stream"
         assert [O.lib().ffo_mt_next(py_rng) for _ in range(4)] == list(ep.py_tail), "py stream"
+
+
+def test_injected_cases_present():
+    names = inject_names()
+    assert len(names) >= 24
+    for room in ("plain", "obstacle", "interior"):
+        for nbh in ("neumann", "moore"):
+            assert any(n.startswith(f"{room}_{nbh}_") for n in names), (room, nbh)
+    assert any(load_inject(n).map.shape == (20, 24) for n in names if "20x24" in n)
+
+
+@pytest.mark.parametrize("name", inject_names())
+def test_oracle_replays_injected_goldens(name):
+    """The reference stepped from injected positions and DFF (packed blobs, rings around one
+    cell, a DFF scale up to 200; tests/golden/gen_injected.py): step_mt replays the cells, the
+    DFF bits and both MT streams."""
+    c = load_inject(name)
+    core = O.Core(c.map, c.sff, c.params)
+    np_rng, py_rng = O.seeded_np(c.seed), O.seeded_py(c.seed)
+    pos = c.pos0.astype(np.int32)
+    dff = c.dff0.copy()
+    for t in range(len(c.counts)):
+        pos = core.step_mt(pos, dff, np_rng, py_rng)
+        assert np.array_equal(pos, c.cells[t]), f"step {t}: positions"
+        assert np.array_equal(dff.view(np.uint32), c.dff[t].view(np.uint32)), f"step {t}: DFF bits"
+    assert [O.lib().ffo_mt_next(np_rng) for _ in range(4)] == list(c.np_tail), "np stream"
+    assert [O.lib().ffo_mt_next(py_rng) for _ in range(4)] == list(c.py_tail), "py stream"
 
 
 def test_mt_streams_match_interpreter():
@@ -77,6 +104,16 @@ def test_np_exp_float32_sampled():
     x = np.concatenate([x, np.float32([0.0, -0.0, -np.inf, -103.9720, -103.97209, -87.3, -1e-30]),
                         -np.abs(rs.standard_normal(1_000_000).astype(np.float32))])
     assert np.array_equal(O.np_expf(x).view(np.uint32), np.exp(x).view(np.uint32))
+
+
+def test_np_exp_float32_below_minus_104():
+    """The exact decide's exp argument (score - max) goes far below -104 under a large DFF:
+    about 1 M float32 from -104 down to -inf by bit pattern, and both ends (all 0)."""
+    x = np_expf_tail_inputs()
+    assert x.size > 1_000_000 and x.max() == np.float32(-104.0) and np.isneginf(x.min())
+    want = np.exp(x)
+    assert not want.any()
+    assert np.array_equal(O.np_expf(x).view(np.uint32), want.view(np.uint32))
 
 
 @pytest.mark.slow
