@@ -200,6 +200,14 @@ void core_group_kernel(CoreStepArgs a) {
     // of 8 envs (zeroed), so a partial last group reads zero counts and DFF and its stores land
     // in the padding; every access takes its group's byte base as the scalar offset, and lanes
     // past the group's bytes use kOOB (dropped).
+    // A launch may also be one env shard of the engine's arrays (engine.cpp, step shards): pos /
+    // cnt / dff / episodes then point at the shard's first env and E is its env count.  Shards
+    // start at multiples of 8 envs, so every shard but the last holds whole groups only (G divides
+    // 8) and its Epad = E: the resources end at the shard's end, every store of a group is
+    // addressed inside that group's envs, and the hardware drops what lies past a resource -- no
+    // store reaches the next shard.  The last shard's partial group lands in the arrays' padding
+    // as before.  Only the position load may read past a shard (G * 64 bytes whatever A is, cut
+    // at the resource's 4 bytes of slack): read-only, of rows this launch does not step.
     const int Epad = (int)((E + 7) & ~7LL);
     const __amdgpu_buffer_rsrc_t rC = pair_rsrc(a.cnt, Epad * 4);
     const __amdgpu_buffer_rsrc_t rP = pair_rsrc(a.pos, Epad * A * 2 + 4);   // + the dword of slack
@@ -572,7 +580,7 @@ void core_group_kernel(CoreStepArgs a) {
         if (c_steps) atomicAdd(&ctr[0], (unsigned long long)c_steps);
         if (c_exits) atomicAdd(&ctr[1], (unsigned long long)c_exits);
         if (c_resets) atomicAdd(&ctr[2], (unsigned long long)c_resets);
-        if (blockIdx.x == 0 && wv == 0) atomicAdd(&ctr[3], 1ull);
+        if (blockIdx.x == 0 && wv == 0 && !a.no_step_count) atomicAdd(&ctr[3], 1ull);
     }
 }
 

@@ -80,7 +80,27 @@ struct ffm_engine {
     unsigned char* d_scratch = nullptr;    // [E][scratch_stride]
     size_t scratch_stride = 0;
     ffm::CoreCapture cap{};      // trajectory capture (n_sel = 0: off)
+    // Step shards (group kernel, ffm_engine_step with n_steps > 1): disjoint env ranges, each
+    // stepped by launches of its own on a stream of its own, so the fill and drain of one
+    // shard's launch overlap the body of the others'.  Shard 0 runs on the caller's stream.
+    struct Shard {
+        long long e0 = 0, n = 0;   // first env, env count (e0 a multiple of 8)
+        int blocks = 0, g = 4;     // its grid and envs per group
+        size_t ctr0 = 0;           // its first counter slot
+    };
+    std::vector<Shard> shards;   // size() <= 1: off
+    hipStream_t sh_stream[3] = {nullptr, nullptr, nullptr};   // shards 1..3
+    hipEvent_t sh_fork = nullptr;
+    hipEvent_t sh_end[3] = {nullptr, nullptr, nullptr};
 };
+
+// Upper bound of FFM_STEP_SHARDS: the caller's stream + 3 of the engine's (a process has 4
+// hardware queues by default; more streams than queues only serialise).
+static constexpr int kMaxStepShards = 4;
+// Default shard count where sharding engages (65,536 envs: 2 shards 26.9 us per step, 3 and 4
+// shards 27.2 - 27.3, one launch 33.9; profiles/step_shards/).
+// Shard 0 runs on the caller's stream, so the engine owns at most 3 streams.
+static constexpr int kDefaultStepShards = 2;
 
 static void free_capture(ffm_engine* e) {
     void* bufs[] = {(void*)e->cap.envs, (void*)e->cap.phase, e->cap.state, e->cap.meta, e->cap.cells, e->cap.n};
@@ -95,6 +115,14 @@ int ffm_abi_version(void) { return FFM_ABI_VERSION; }
 
 static void release(ffm_engine* e) {
     if (!e) return;
+    for (int i = 0; i < 3; i++) {
+        if (e->sh_stream[i]) {
+            (void)hipStreamSynchronize(e->sh_stream[i]);
+            (void)hipStreamDestroy(e->sh_stream[i]);
+        }
+        if (e->sh_end[i]) (void)hipEventDestroy(e->sh_end[i]);
+    }
+    if (e->sh_fork) (void)hipEventDestroy(e->sh_fork);
     (void)hipFree(e->d_map);
     (void)hipFree(e->d_sff);
     (void)hipFree(e->d_free);
@@ -253,6 +281,7 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
     int cus = 0;
     he = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d.device);
     if (he != hipSuccess) return cleanup(fail(FFM_E_HIP, "hipDeviceGetAttribute"));
+    size_t shard_slots = 0;   // counter slots of the step shards, one range each
     {
         ffm::CoreStepArgs a{};
         a.H = H; a.W = W; a.A = A; a.F = e->F; a.auto_reset = reset_lds;
@@ -288,23 +317,63 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
             }
         }
         if (e->group) {
-            e->group_g = ffm::core_group_pick_envs(a, d.neighborhood, d.n_envs, cus);
-            const int per_cu = std::max(1, ffm::core_group_blocks_per_cu(a, d.neighborhood, e->group_g));
-            const long long G = e->group_g;
-            const long long groups = (d.n_envs + G - 1) / G;
             // at most 6 blocks (6 waves per SIMD) per CU: the group kernel fits 7 (71 VGPRs), but 7
             // waves per SIMD step slower (65,536 envs 36.0 vs 33.0 us, 32,768 envs 23.1 vs 21.6 us),
             // and fewer blocks than 6 per CU are slower too (1,366 blocks 36.5 us; 1,024 blocks at
             // 32,768 envs 23.6 us): profiles/r06/c2/ab_grid_balance*.log, ab_occupancy7.log
-            const long long bpc = std::min(per_cu, 6);
-            e->group_blocks = (int)std::max<long long>(1, std::min<long long>((groups + 3) / 4, (long long)cus * bpc));
-            if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {   // diagnostic override of the grid
-                const long long v = std::atoll(ov);
-                if (v > 0) e->group_blocks = (int)std::min<long long>(v, (groups + 3) / 4);
+            auto resident_cap = [&](int G) {
+                const int per_cu = std::max(1, ffm::core_group_blocks_per_cu(a, d.neighborhood, G));
+                return (long long)cus * std::min(per_cu, 6);
+            };
+            // the persistent grid of a launch of n envs
+            auto group_grid = [&](long long n, int G) {
+                const long long groups = (n + G - 1) / G;
+                long long b = std::max<long long>(1, std::min<long long>((groups + 3) / 4, resident_cap(G)));
+                if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {   // diagnostic override of the grid
+                    const long long v = std::atoll(ov);
+                    if (v > 0) b = std::min<long long>(v, (groups + 3) / 4);
+                }
+                // every wave steps at most core_group_max_iters() groups (its deferred-reset mask)
+                const long long per_wave = ffm::core_group_max_iters();
+                return (int)std::max<long long>(b, (groups + 4 * per_wave - 1) / (4 * per_wave));
+            };
+            e->group_g = ffm::core_group_pick_envs(a, d.neighborhood, d.n_envs, cus);
+            e->group_blocks = group_grid(d.n_envs, e->group_g);
+
+            // Step shards.  FFM_STEP_SHARDS=1..4 forces the count (A/B switch, read at create);
+            // unset, kDefaultStepShards shards wherever the one-launch grid has its waves step two
+            // or more groups (on MI355X from 24,577 envs on; two shards measured faster from
+            // 8,192 envs on, but below that size the engine keeps the single launch its callers
+            // and the geometry tests know).  Every shard launches the persistent grid its env
+            // count would get alone: the shards alternate on the GPU, and the slots a draining
+            // launch frees take the next shard's blocks (1 / S of the resident blocks per shard
+            // measured slower: profiles/step_shards/).
+            int S = kDefaultStepShards;
+            const long long groups = (d.n_envs + e->group_g - 1) / e->group_g;
+            if (groups <= resident_cap(e->group_g) * 4) S = 1;
+            if (const char* ov = std::getenv("FFM_STEP_SHARDS")) {
+                const int v = std::atoi(ov);
+                if (v >= 1 && v <= kMaxStepShards) S = v;
             }
-            // every wave steps at most core_group_max_iters() groups (its deferred-reset mask)
-            const long long per_wave = ffm::core_group_max_iters();
-            e->group_blocks = (int)std::max<long long>(e->group_blocks, (groups + 4 * per_wave - 1) / (4 * per_wave));
+            if (S > 1) {
+                // contiguous shards whose boundaries are multiples of 8 envs: only the last can
+                // hold a partial group, whose stores land in the arrays' zeroed padding
+                // (core_group.hip); empty shards are skipped
+                const long long per = ((d.n_envs + S - 1) / S + 7) & ~7ll;
+                size_t ctr0 = 0;
+                for (long long e0 = 0; e0 < d.n_envs; e0 += per) {
+                    ffm_engine::Shard sh;
+                    sh.e0 = e0;
+                    sh.n = std::min<long long>(per, d.n_envs - e0);
+                    sh.g = ffm::core_group_pick_envs(a, d.neighborhood, sh.n, cus);
+                    sh.blocks = group_grid(sh.n, sh.g);
+                    sh.ctr0 = ctr0;           // a slot range per shard: never contended on the device
+                    ctr0 += (size_t)sh.blocks * 4;
+                    e->shards.push_back(sh);
+                }
+                shard_slots = ctr0;
+                if (e->shards.size() <= 1) e->shards.clear();
+            }
         }
     }
     // One counter slot per wave (wave / lane kernel) or block (block kernel):
@@ -315,6 +384,17 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
         e->ctr_slots = (size_t)std::max<long long>(std::max<long long>(std::max<long long>(1, blocks),
                                                                        (groups + 3) / 4 * 4),
                                                    (long long)std::max(std::max(e->lane_blocks, e->group_blocks), e->multi_blocks) * 4);
+        e->ctr_slots = std::max(e->ctr_slots, shard_slots);
+    }
+    // the shards' streams (shard 0 runs on the caller's) and the fork / join events
+    if (!e->shards.empty()) {
+        he = hipEventCreateWithFlags(&e->sh_fork, hipEventDisableTiming);
+        for (size_t i = 0; he == hipSuccess && i + 1 < e->shards.size(); i++) {
+            he = hipStreamCreateWithFlags(&e->sh_stream[i], hipStreamNonBlocking);
+            if (he == hipSuccess) he = hipEventCreateWithFlags(&e->sh_end[i], hipEventDisableTiming);
+        }
+        if (he != hipSuccess)
+            return cleanup(fail(FFM_E_HIP, std::string("step shard streams: ") + hipGetErrorString(he)));
     }
     ALLOC(e->d_ctr, e->ctr_slots * 32);
     ALLOC(e->d_dbg, 16 * 8);
@@ -393,6 +473,57 @@ static ffm::CoreStepArgs make_args(ffm_engine* e) {
     return a;
 }
 
+// Shards a step(n > 1) call runs as, under the engine's current settings: 1 (one launch per
+// step over all envs) with trajectory capture on (its kernel follows every step launch on the
+// caller's stream) and on the fused multi-step path.
+static int shards_in_effect(const ffm_engine* e) {
+    if (e->shards.size() <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi)) return 1;
+    return (int)e->shards.size();
+}
+
+// n_steps steps as one launch per step and shard.  One fork and one join per call: the shard
+// streams wait for what the caller's stream holds so far, the launches go out step-major (so
+// the queues fill evenly from this one thread), and the caller's stream waits for every
+// shard's last launch.  In between the shards drift freely: step t + 1 of a shard needs step t
+// of that shard only (envs are independent, every draw is keyed by (t, global env)).  Whatever
+// else the engine enqueues uses the caller's stream and is ordered by the join.
+static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
+    const size_t S = e->shards.size();
+    const int A = e->d.agent_capacity;
+    HIP_TRY(hipEventRecord(e->sh_fork, s));
+    for (size_t k = 1; k < S; k++) HIP_TRY(hipStreamWaitEvent(e->sh_stream[k - 1], e->sh_fork, 0));
+    const ffm::CoreStepArgs base = make_args(e);
+    hipError_t he = hipSuccess;
+    int done = 0;
+    for (; done < n_steps && he == hipSuccess; done++) {
+        for (size_t k = 0; k < S && he == hipSuccess; k++) {
+            const ffm_engine::Shard& sh = e->shards[k];
+            ffm::CoreStepArgs a = base;
+            a.t = e->t + (uint32_t)done;
+            a.E = sh.n;
+            a.env_base = base.env_base + sh.e0;
+            a.pos = base.pos + sh.e0 * A;
+            a.cnt = base.cnt + sh.e0;
+            a.dff = base.dff + sh.e0 * e->HW;
+            a.episodes = base.episodes + sh.e0;
+            a.counters = base.counters + 4 * sh.ctr0;
+            a.no_step_count = k != 0;   // one shard per step counts the step
+            he = ffm::launch_core_group(a, e->d.neighborhood, sh.blocks, k ? e->sh_stream[k - 1] : s, sh.g);
+        }
+    }
+    // the join also after a failed launch: what was enqueued stays ordered before the caller's next work
+    hipError_t hj = hipSuccess;
+    for (size_t k = 1; k < S; k++) {
+        hipError_t h1 = hipEventRecord(e->sh_end[k - 1], e->sh_stream[k - 1]);
+        if (h1 == hipSuccess) h1 = hipStreamWaitEvent(s, e->sh_end[k - 1], 0);
+        if (h1 != hipSuccess) hj = h1;
+    }
+    if (he != hipSuccess) return fail(FFM_E_HIP, std::string("launch_core_group (step shard): ") + hipGetErrorString(he));
+    e->t += (uint32_t)n_steps;
+    if (hj != hipSuccess) return fail(FFM_E_HIP, std::string("step shard join: ") + hipGetErrorString(hj));
+    return FFM_OK;
+}
+
 int ffm_engine_step(ffm_engine* e, int32_t n_steps, void* stream) {
     if (!e || n_steps < 0) return fail(FFM_E_INVALID, "bad engine/n_steps");
     hipStream_t s = (hipStream_t)stream;
@@ -406,6 +537,16 @@ int ffm_engine_step(ffm_engine* e, int32_t n_steps, void* stream) {
             done += k;
         }
         return FFM_OK;
+    }
+    if (shards_in_effect(e) > 1 && n_steps > 1) {
+        // a stream under capture keeps today's single launch per step (no fork into streams
+        // the capture does not know)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess) {
+            (void)hipGetLastError();
+            cs = hipStreamCaptureStatusActive;
+        }
+        if (cs == hipStreamCaptureStatusNone) return step_sharded(e, n_steps, s);
     }
     for (int i = 0; i < n_steps; i++) {
         ffm::CoreStepArgs a = make_args(e);
@@ -684,19 +825,25 @@ int ffm_debug_read(ffm_engine* e, uint64_t* out, int n) {
 //   out[3] K, envs per workgroup of the block kernel
 //   out[4] threads per block of the step kernel
 //   out[5] 1 if the fused multi-step kernel is available, out[6] its grid's blocks
+//   out[7] env shards a step(n > 1) call runs as under the current settings (1: one launch per
+//          step over all envs), out[8] blocks of one shard's grid (the first's; out[2] if one shard)
 int ffm_debug_launch_info(ffm_engine* e, int32_t* out, int n) {
-    if (!e || !out || n < 0 || n > 7) return fail(FFM_E_INVALID, "bad args");
+    if (!e || !out || n < 0 || n > 9) return fail(FFM_E_INVALID, "bad args");
     const int kernel = e->group ? 0 : e->lane ? 1 : e->wave ? 2 : e->big ? 4 : 3;
     const long long E = e->d.n_envs;
-    const int32_t v[7] = {
+    const int S = shards_in_effect(e);
+    const int32_t step_blocks = e->group ? e->group_blocks : e->lane ? e->lane_blocks : e->wave ? e->wave_blocks
+                                                                                              : (int32_t)((E + e->K - 1) / e->K);
+    const int32_t v[9] = {
         kernel,
         e->group ? e->group_g : 0,
-        e->group ? e->group_blocks : e->lane ? e->lane_blocks : e->wave ? e->wave_blocks
-                                                                        : (int32_t)((E + e->K - 1) / e->K),
+        step_blocks,
         e->K,
         kernel <= 2 ? 256 : e->big ? 1024 : e->block,
         e->multi ? 1 : 0,
         e->multi ? e->multi_blocks : 0,
+        S,
+        S > 1 ? e->shards[0].blocks : step_blocks,
     };
     for (int i = 0; i < n; i++) out[i] = v[i];
     return FFM_OK;

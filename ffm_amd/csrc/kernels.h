@@ -41,6 +41,8 @@ struct CoreStepArgs {
     unsigned long long* dbg;  // diagnostic builds: [16] per-phase cycle sums (else unused)
     unsigned char* scratch;   // big maps: [blocks][scratch_stride] block state (else nullptr)
     size_t scratch_stride;
+    int no_step_count;        // group kernel: this launch leaves the `steps` counter alone (an env shard
+                              // other than the step's first: engine.cpp, step shards)
 };
 
 // Trajectory capture of the batched ffm_core step (ffm_engine_set_trajectory_capture):

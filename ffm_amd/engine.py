@@ -465,12 +465,14 @@ class Engine:
         """The launch geometry chosen at create (diagnostic, ffm_debug_launch_info): the step
         kernel ("group", "lane", "wave", "block" or "block_scratch"), the group kernel's envs per
         group (0 for the other kernels), the step grid's blocks, the block kernel's envs per
-        workgroup K, the block size, and the fused multi-step kernel's availability and grid."""
-        v = np.zeros(7, np.int32)
+        workgroup K, the block size, the fused multi-step kernel's availability and grid, and the
+        env shards a step(n > 1) call runs as under the current settings (1 = one launch per step
+        over all envs) with the blocks of one shard's grid."""
+        v = np.zeros(9, np.int32)
         _check(self._L.ffm_debug_launch_info(self._h, _ptr(v), len(v)))
         return {"kernel": ("group", "lane", "wave", "block", "block_scratch")[int(v[0])], "group_g": int(v[1]),
                 "blocks": int(v[2]), "K": int(v[3]), "block_size": int(v[4]), "multi": bool(v[5]),
-                "multi_blocks": int(v[6])}
+                "multi_blocks": int(v[6]), "step_shards": int(v[7]), "shard_blocks": int(v[8])}
 
     @property
     def step_index(self) -> int:

@@ -125,7 +125,11 @@ int ffm_engine_reset(ffm_engine* eng, void* stream);
  * (an abandoned episode is not a completed one).  MT mode: FFM_E_UNSUPPORTED. */
 int ffm_engine_reset_envs(ffm_engine* eng, const uint8_t* mask, void* stream);
 
-/* Advance every env by n_steps steps (model/ffm_core.py:36-104 each). */
+/* Advance every env by n_steps steps (model/ffm_core.py:36-104 each).  With n_steps > 1 a
+ * large 12x12 Philox engine may step disjoint env ranges on streams of its own between one
+ * fork from and one join into `stream` (DESIGN.md section 4, step shards): whatever follows
+ * on `stream` sees all n_steps steps of every env, and the state is the same bits either way.
+ * A stream under capture always gets one launch per step on that stream. */
 int ffm_engine_step(ffm_engine* eng, int32_t n_steps, void* stream);
 
 /* Steps fused per launch by ffm_engine_step (default 1: one launch per step).
