@@ -39,6 +39,7 @@
 #include "core_common.h"
 #include "kernels.h"
 #include "lane_common.h"
+#include "episode_log.h"
 #include "wave_reset.h"
 
 namespace ffm {
@@ -140,7 +141,9 @@ __device__ __forceinline__ int cs_xp1(uint32_t v) { return (int)(v >> 25); }
 #define FFM_GROUP_WAVES 6   // minimum waves per SIMD asked of the register allocator (G = 4 needs 71 VGPRs; the grid holds 6 per SIMD)
 #endif
 
-template <int NB, int HT, int WT, int G, bool KD1>
+// EPL: the episode log (episode_log.h) as a kernel of its own, as KD1 is (group_op): behind a
+// runtime pointer its code costs the step 4 VGPRs with the log off.
+template <int NB, int HT, int WT, int G, bool KD1, bool EPL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FFM_GROUP_WAVES, 8)))
 void core_group_kernel(CoreStepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -486,6 +489,10 @@ void core_group_kernel(CoreStepArgs a) {
             if (a.episodes && rs) a.episodes[e0 + lane] += 1;
             if (lane == 0) pend[iter >> 2] |= (uint32_t)rsm << (8 * (iter & 3));
         }
+        // episode log (episode_log.h): with auto_reset every ended env is in rsm, so the
+        // ballot of ending lanes is taken inside that rare branch only
+        if (EPL && (rsm || !a.auto_reset))
+            eplog_end_wave(a, lane < nenv && nk == 0 && Sh > Sl, rs, e0 + lane, a.t, lane);
         }   // LAD >= 3
 
         // ---- next group's HBM loads, in flight across the stencil, the stores and the
@@ -611,7 +618,7 @@ static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int
     const size_t smem = core_group_smem_bytes(a.H, a.W, a.F, 4, G);
     if (op) {
         *occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1>, 256, smem) !=
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1, false>, 256, smem) !=
             hipSuccess)
             *occ = 0;
         return hipSuccess;
@@ -619,7 +626,8 @@ static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int
     const long long groups = (a.E + G - 1) / G;
     if (a.H != 12 || a.W != 12 || a.A > 32 || (groups + (long long)blocks * 4 - 1) / ((long long)blocks * 4) > kGroupMaxIters)
         return hipErrorInvalidConfiguration;   // shapes the kernel and its grid assume
-    core_group_kernel<NB, 12, 12, G, KD1><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
+    if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
+    else core_group_kernel<NB, 12, 12, G, KD1, false><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
     return hipGetLastError();
 }
 

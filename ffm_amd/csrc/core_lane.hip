@@ -32,6 +32,7 @@
 #include "core_common.h"
 #include "kernels.h"
 #include "lane_common.h"
+#include "episode_log.h"
 #include "wave_reset.h"
 
 #ifndef FFM_STAMPS
@@ -100,7 +101,7 @@ __host__ __device__ inline size_t lane_shared_bytes(int PHW, int F) {
 template <int NB, int HT>
 constexpr int lane_waves() { return (NB == 4 && HT == 12) ? FFM_LANE_WAVES : 1; }
 
-template <int NB, int HT, int WT>
+template <int NB, int HT, int WT, bool EPL>   // EPL: with the episode log (episode_log.h)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lane_waves<NB, HT>(), 8)))
 void core_lane_kernel(CoreStepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -313,6 +314,9 @@ void core_lane_kernel(CoreStepArgs a) {
             const uint32_t bits = (uint32_t)((rsm & 1ull) | (((rsm >> 32) & 1ull) << 1)) << ((2 * iter) & 31);
             if (lane == 0) pend[(2 * iter) >> 5] |= bits;
         }
+        // episode log (episode_log.h): with auto_reset every ended env is in rsm
+        if (EPL && (rsm || !a.auto_reset))
+            eplog_end_wave(a, env_ok && al == 0 && newcnt == 0 && cnt > 0, rs && al == 0, e0 + sub, a.t, lane);
 
         LSTAMP(4);
         // ---- next group's HBM loads, in flight across the stencil, the stores and the
@@ -411,11 +415,12 @@ static hipError_t lane_op(const CoreStepArgs& a, int blocks, hipStream_t s, int 
         return hipErrorInvalidConfiguration;   // the grid must give every wave <= kLaneMaxPairs pairs
     if (op) {
         *occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_lane_kernel<NB, HT, WT>, 256, smem) != hipSuccess)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_lane_kernel<NB, HT, WT, false>, 256, smem) != hipSuccess)
             *occ = 0;
         return hipSuccess;
     }
-    core_lane_kernel<NB, HT, WT><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
+    if (a.ep_start) core_lane_kernel<NB, HT, WT, true><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
+    else core_lane_kernel<NB, HT, WT, false><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
     return hipGetLastError();
 }
 

@@ -24,6 +24,7 @@
 #include "core_common.h"
 #include "kernels.h"
 #include "lane_common.h"
+#include "episode_log.h"
 #include "wave_reset.h"
 
 namespace ffm {
@@ -56,7 +57,7 @@ __host__ __device__ inline size_t multi_shared_bytes(int PHW, int F) {
 #define FFM_MULTI_WAVES 1   // minimum waves per SIMD asked of the register allocator
 #endif
 
-template <int NB, int HT, int WT>
+template <int NB, int HT, int WT, bool EPL>   // EPL: with the episode log (episode_log.h)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FFM_MULTI_WAVES, 8)))
 void core_multi_kernel(CoreStepArgs a, int nsteps) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -217,6 +218,10 @@ void core_multi_kernel(CoreStepArgs a, int nsteps) {
                 for (int s = 0; s < 2; s++)
                     if ((rsm >> (32 * s)) & 1ull) wave_reset_env(ak, ebase + (uint32_t)(e0 + s), keys, pfree, posb + s * 32, lane);
             }
+            // episode log (episode_log.h), keyed by the inner step's index; with auto_reset
+            // every ended env is in rsm
+            if (EPL && (rsm || !a.auto_reset))
+                eplog_end_wave(a, env_ok && al == 0 && newcnt == 0 && cnt > 0, rs && al == 0, e0 + sub, t, lane);
             cnt = rs ? a.N : newcnt;
             wave_sync();
             cpos = posb[lane];
@@ -289,13 +294,14 @@ static hipError_t multi_op(const CoreStepArgs& a, int nsteps, int blocks, hipStr
     const size_t smem = core_multi_smem_bytes(a.H, a.W, a.F, 4);
     if (op) {
         *occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_multi_kernel<NB, HT, WT>, 256, smem) != hipSuccess)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_multi_kernel<NB, HT, WT, false>, 256, smem) != hipSuccess)
             *occ = 0;
         return hipSuccess;
     }
     if (a.A > 32 || a.N > 32 || a.W % 4 != 0 || a.H * a.W > 256 || nsteps < 1)
         return hipErrorInvalidConfiguration;   // shapes the kernel assumes
-    core_multi_kernel<NB, HT, WT><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a, nsteps);
+    if (a.ep_start) core_multi_kernel<NB, HT, WT, true><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a, nsteps);
+    else core_multi_kernel<NB, HT, WT, false><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a, nsteps);
     return hipGetLastError();
 }
 

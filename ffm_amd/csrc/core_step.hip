@@ -40,6 +40,7 @@
 #include "core_common.h"
 #include "kernels.h"
 #include "lane_common.h"
+#include "episode_log.h"
 #include "wave_reset.h"
 
 #ifndef FFM_STAMPS
@@ -139,7 +140,9 @@ struct WavePrefetch {
     int cnt;
 };
 
-template <int NB, bool MT, int EW, int HT, int WT>
+// EPL: with the episode log (episode_log.h; Philox only) -- a kernel of its own, so that
+// the log's code costs the step no registers while it is off.
+template <int NB, bool MT, int EW, int HT, int WT, bool EPL>
 __global__ __launch_bounds__(256)
 #if FFM_WAVES_PER_EU
 __attribute__((amdgpu_waves_per_eu(FFM_WAVES_PER_EU)))
@@ -476,6 +479,10 @@ void core_wave_kernel(CoreStepArgs a) {
             if (al == 0 && env_ok) {
                 gc[sub] = rs ? a.N : newcnt;
                 if (rs && a.episodes) a.episodes[e0 + sub] += 1;
+                if (EPL) {   // episode log (episode_log.h)
+                    if (newcnt == 0 && cnt > 0) eplog_end_one(a, e0 + sub, a.t);
+                    else if (rs) a.ep_start[e0 + sub] = a.t;
+                }
             }
             // a reset env starts its next episode with a zero DFF
             const int zs0 = (4 * lane) / HW, zs1 = (4 * (lane + 64)) / HW;
@@ -714,7 +721,7 @@ __device__ __forceinline__ CT req_cell(uint32_t slot, int pp, int PW) {
 // The Neumann float32 kernels fit 8 waves per SIMD (57 VGPRs, 78 SGPRs, no spills) and with
 // the placement keys sharing the dead arrays' LDS (block_carve) four 512-lane blocks fit a
 // CU: C3 137.3 -> 129.7 us.  Moore and float64 would spill under that bound: theirs stays 1.
-template <int NB, bool F64, bool MT, int BS, bool BIG>
+template <int NB, bool F64, bool MT, int BS, bool BIG, bool EPL>   // EPL: as core_wave_kernel's
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(NB == 4 && !F64 ? FFM_BLOCK_WAVES : 1, 8)))
 void core_block_kernel(CoreStepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1011,6 +1018,10 @@ void core_block_kernel(CoreStepArgs a) {
     if (tid < K) {
         a.cnt[e0 + tid] = sreset[tid] ? a.N : snew[tid];
         if (sreset[tid] && a.episodes) a.episodes[e0 + tid] += 1;
+        if (EPL) {   // episode log (episode_log.h)
+            if (snew[tid] == 0 && scnt[tid] > 0) eplog_end_one(a, e0 + tid, a.t);
+            else if (sreset[tid]) a.ep_start[e0 + tid] = a.t;
+        }
     }
 
     // ---- update_dff (model/ffm_core.py:106-117) --------------------------------------------------
@@ -1084,7 +1095,10 @@ __global__ __launch_bounds__(64) void core_reset_kernel(CoreStepArgs a, const ui
     for (int i = threadIdx.x; i < a.F; i += 64) fl[i] = a.free_padded[i];
     wave_sync();
     wave_reset_env(a, (uint32_t)(a.env_base + e), keys, fl, a.pos + e * a.A, threadIdx.x);
-    if (threadIdx.x == 0) a.cnt[e] = a.N;
+    if (threadIdx.x == 0) {
+        a.cnt[e] = a.N;
+        eplog_mark_start(a, e, a.t);
+    }
 }
 
 // Reset every env of a map whose free list does not fit the wave reset's LDS
@@ -1101,7 +1115,10 @@ __global__ __launch_bounds__(1024) void core_block_reset_kernel(CoreStepArgs a, 
     const BlockCarve cv = block_carve((a.H + 2) * (a.W + 2), a.A, 1, a.F, false, false, true, true);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(a.scratch + (size_t)e * a.scratch_stride + cv.keys);
     block_place_env<1024>(a, e, keys, block_keys_cap(a.A, a.F), swsum);
-    if (threadIdx.x == 0) a.cnt[e] = a.N;
+    if (threadIdx.x == 0) {
+        a.cnt[e] = a.N;
+        eplog_mark_start(a, e, a.t);
+    }
 }
 
 // ===========================================================================
@@ -1139,7 +1156,8 @@ __global__ void np_expf_kernel(const float* __restrict__ x, float* __restrict__ 
 template <int NB, bool MT, int EW, int HT, int WT>
 static hipError_t launch_wave_t(const CoreStepArgs& a, int blocks, hipStream_t s) {
     const size_t smem = core_wave_smem_bytes(a.H, a.W, a.A, a.F, MT, !MT && a.auto_reset, 4) + FFM_LDS_PAD;
-    core_wave_kernel<NB, MT, EW, HT, WT><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
+    if (!MT && a.ep_start) core_wave_kernel<NB, MT, EW, HT, WT, !MT><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
+    else core_wave_kernel<NB, MT, EW, HT, WT, false><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
     return hipGetLastError();
 }
 
@@ -1147,7 +1165,7 @@ template <int NB, bool MT, int EW, int HT, int WT>
 static int occ_wave_t(const CoreStepArgs& a) {
     const size_t smem = core_wave_smem_bytes(a.H, a.W, a.A, a.F, MT, !MT && a.auto_reset, 4) + FFM_LDS_PAD;
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, core_wave_kernel<NB, MT, EW, HT, WT>, 256, smem) != hipSuccess)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, core_wave_kernel<NB, MT, EW, HT, WT, false>, 256, smem) != hipSuccess)
         return 0;
     return n;
 }
@@ -1189,14 +1207,19 @@ static hipError_t launch_block_t(const CoreStepArgs& a, int block, hipStream_t s
     const long long nblk = (a.E + a.K - 1) / a.K;
     if (a.scratch) {   // big maps: K = 1, state in global scratch
         const size_t smem = block_carve((a.H + 2) * (a.W + 2), a.A, 1, a.F, F64, MT, true, true).lds;
-        core_block_kernel<NB, F64, MT, 1024, true><<<dim3((unsigned)nblk), dim3(1024), smem, s>>>(a);
+        if (!MT && a.ep_start)
+            core_block_kernel<NB, F64, MT, 1024, true, !MT><<<dim3((unsigned)nblk), dim3(1024), smem, s>>>(a);
+        else core_block_kernel<NB, F64, MT, 1024, true, false><<<dim3((unsigned)nblk), dim3(1024), smem, s>>>(a);
         return hipGetLastError();
     }
     const size_t smem = core_block_smem_bytes(a.H, a.W, a.A, a.K, a.F, F64, MT, !MT && a.auto_reset);
+    const bool epl = !MT && a.ep_start;
     if (block == 512) {
-        core_block_kernel<NB, F64, MT, 512, false><<<dim3((unsigned)nblk), dim3(512), smem, s>>>(a);
+        if (epl) core_block_kernel<NB, F64, MT, 512, false, !MT><<<dim3((unsigned)nblk), dim3(512), smem, s>>>(a);
+        else core_block_kernel<NB, F64, MT, 512, false, false><<<dim3((unsigned)nblk), dim3(512), smem, s>>>(a);
     } else {
-        core_block_kernel<NB, F64, MT, 256, false><<<dim3((unsigned)nblk), dim3(256), smem, s>>>(a);
+        if (epl) core_block_kernel<NB, F64, MT, 256, false, !MT><<<dim3((unsigned)nblk), dim3(256), smem, s>>>(a);
+        else core_block_kernel<NB, F64, MT, 256, false, false><<<dim3((unsigned)nblk), dim3(256), smem, s>>>(a);
     }
     return hipGetLastError();
 }

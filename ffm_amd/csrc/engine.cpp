@@ -80,6 +80,13 @@ struct ffm_engine {
     unsigned char* d_scratch = nullptr;    // [E][scratch_stride]
     size_t scratch_stride = 0;
     ffm::CoreCapture cap{};      // trajectory capture (n_sel = 0: off)
+    // Episode log and statistics (ffm_engine_set_episode_log): all null / 0 while off.
+    uint32_t* d_ep_start = nullptr;           // [n_envs padded to 8] step index of each env's placement
+    int32_t* d_eplog = nullptr;               // [eplog_cap][4]
+    unsigned long long* d_eplog_n = nullptr;  // records appended
+    long long eplog_cap = 0;
+    unsigned long long* d_ephist = nullptr;   // [ephist_bins] histogram, then the summary's slots
+    int ephist_bins = 0;
     // Step shards (group kernel, ffm_engine_step with n_steps > 1): disjoint env ranges, each
     // stepped by launches of its own on a stream of its own, so the fill and drain of one
     // shard's launch overlap the body of the others'.  Shard 0 runs on the caller's stream.
@@ -101,6 +108,25 @@ static constexpr int kMaxStepShards = 4;
 // shards 27.2 - 27.3, one launch 33.9; profiles/step_shards/).
 // Shard 0 runs on the caller's stream, so the engine owns at most 3 streams.
 static constexpr int kDefaultStepShards = 2;
+
+// d_ephist: the histogram, then (on a 128-byte boundary) the summary's slots (kernels.h).
+static size_t ep_sum_offset(int bins) { return ((size_t)bins + 15) & ~(size_t)15; }
+static size_t ep_stats_words(int bins) { return ep_sum_offset(bins) + (size_t)ffm::kEpSumSlots * ffm::kEpSumStride; }
+
+static void free_episode_log(ffm_engine* e, bool ep_start_too) {
+    (void)hipFree(e->d_eplog);
+    (void)hipFree(e->d_eplog_n);
+    (void)hipFree(e->d_ephist);
+    e->d_eplog = nullptr;
+    e->d_eplog_n = nullptr;
+    e->d_ephist = nullptr;
+    e->eplog_cap = 0;
+    e->ephist_bins = 0;
+    if (ep_start_too) {
+        (void)hipFree(e->d_ep_start);
+        e->d_ep_start = nullptr;
+    }
+}
 
 static void free_capture(ffm_engine* e) {
     void* bufs[] = {(void*)e->cap.envs, (void*)e->cap.phase, e->cap.state, e->cap.meta, e->cap.cells, e->cap.n};
@@ -138,6 +164,7 @@ static void release(ffm_engine* e) {
     (void)hipFree(e->d_dbg);
     (void)hipFree(e->d_scratch);
     free_capture(e);
+    free_episode_log(e, true);
     delete e;
 }
 
@@ -470,6 +497,13 @@ static ffm::CoreStepArgs make_args(ffm_engine* e) {
     a.dbg = e->d_dbg;
     a.scratch = e->big ? e->d_scratch : nullptr;
     a.scratch_stride = e->scratch_stride;
+    a.ep_start = e->d_ep_start;
+    a.eplog = e->d_eplog;
+    a.eplog_n = e->d_eplog_n;
+    a.eplog_cap = e->eplog_cap;
+    a.ephist = e->d_ephist;
+    a.ephist_bins = e->ephist_bins;
+    a.epsum = e->d_ephist ? e->d_ephist + ep_sum_offset(e->ephist_bins) : nullptr;
     return a;
 }
 
@@ -506,6 +540,7 @@ static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
             a.cnt = base.cnt + sh.e0;
             a.dff = base.dff + sh.e0 * e->HW;
             a.episodes = base.episodes + sh.e0;
+            if (base.ep_start) a.ep_start = base.ep_start + sh.e0;   // records carry global ids through env_base
             a.counters = base.counters + 4 * sh.ctr0;
             a.no_step_count = k != 0;   // one shard per step counts the step
             he = ffm::launch_core_group(a, e->d.neighborhood, sh.blocks, k ? e->sh_stream[k - 1] : s, sh.g);
@@ -771,6 +806,98 @@ int ffm_engine_drain_trajectory(ffm_engine* e, int32_t* meta, uint16_t* cells, i
     HIP_TRY(hipStreamSynchronize(s));
     *n = have;
     if (dropped) *dropped = (int64_t)c - have;
+    return FFM_OK;
+}
+
+// The statistics' empty state is all zeros (the min is kept inverted).
+static hipError_t clear_episode_stats(ffm_engine* e, hipStream_t s) {
+    return hipMemsetAsync(e->d_ephist, 0, ep_stats_words(e->ephist_bins) * 8, s);
+}
+
+int ffm_engine_set_episode_log(ffm_engine* e, int64_t capacity_records, int32_t hist_bins, void* stream) {
+    if (!e) return fail(FFM_E_INVALID, "null engine");
+    if (e->mt) return fail(FFM_E_UNSUPPORTED, "episode log: Philox engines only");
+    if (capacity_records < 0 || hist_bins < 0) return fail(FFM_E_INVALID, "episode log: negative capacity or bins");
+    if (e->d.env_base < 0 || e->d.env_base + e->d.n_envs > (int64_t)INT32_MAX)
+        return fail(FFM_E_INVALID, "episode log: env_base + n_envs must fit int32 (records hold global env ids)");
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipStreamSynchronize(s));        // queued steps may still write the old buffers
+    const bool off = capacity_records == 0 && hist_bins == 0;
+    free_episode_log(e, off);
+    if (off) return FFM_OK;
+    hipError_t he = hipSuccess;
+    const bool fresh = e->d_ep_start == nullptr;
+    const size_t Ep = ((size_t)e->d.n_envs + 7) & ~(size_t)7;   // padded like d_cnt
+    if (fresh) he = hipMalloc((void**)&e->d_ep_start, Ep * 4);
+    if (he == hipSuccess && capacity_records > 0) {
+        he = hipMalloc((void**)&e->d_eplog, (size_t)capacity_records * 16);
+        if (he == hipSuccess) he = hipMalloc((void**)&e->d_eplog_n, 8);
+    }
+    if (he == hipSuccess && hist_bins > 0) he = hipMalloc((void**)&e->d_ephist, ep_stats_words(hist_bins) * 8);
+    if (he != hipSuccess) {
+        free_episode_log(e, true);
+        return fail(FFM_E_NOMEM, std::string("episode log: ") + hipGetErrorString(he));
+    }
+    e->eplog_cap = e->d_eplog ? capacity_records : 0;
+    e->ephist_bins = e->d_ephist ? hist_bins : 0;
+    // Turned on mid-run: episodes in flight count from here.  The next step is keyed e->t, so
+    // the index that "placed" every env is the one before it (a reset overwrites it anyway).
+    if (fresh) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)e->d_ep_start, (int)(e->t - 1u), Ep, s));
+    if (e->d_eplog_n) HIP_TRY(hipMemsetAsync(e->d_eplog_n, 0, 8, s));
+    if (e->d_ephist) HIP_TRY(clear_episode_stats(e, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return FFM_OK;
+}
+
+int ffm_engine_drain_episodes(ffm_engine* e, int32_t* records, int64_t cap, int64_t* n, int64_t* dropped,
+                              void* stream) {
+    if (!e || !n) return fail(FFM_E_INVALID, "null argument");
+    *n = 0;
+    if (dropped) *dropped = 0;
+    if (!e->d_eplog) return FFM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long c = 0;
+    HIP_TRY(hipMemcpyAsync(&c, e->d_eplog_n, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const long long have = std::min<long long>((long long)c, e->eplog_cap);
+    if (have > cap || (have > 0 && !records)) {
+        *n = have;
+        return fail(FFM_E_INVALID, "drain_episodes: buffer too small (*n holds the count)");
+    }
+    if (have > 0) HIP_TRY(hipMemcpyAsync(records, e->d_eplog, (size_t)have * 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(e->d_eplog_n, 0, 8, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *n = have;
+    if (dropped) *dropped = (int64_t)c - have;
+    return FFM_OK;
+}
+
+int ffm_engine_get_episode_stats(ffm_engine* e, uint64_t* hist, int32_t bins, uint64_t* summary, int32_t clear,
+                                 void* stream) {
+    if (!e) return fail(FFM_E_INVALID, "null engine");
+    if (hist && bins != e->ephist_bins) return fail(FFM_E_INVALID, "episode stats: bins differs from the histogram's");
+    if (summary) std::memset(summary, 0, 5 * sizeof(uint64_t));
+    if (!e->d_ephist) return FFM_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (hist) HIP_TRY(hipMemcpyAsync(hist, e->d_ephist, (size_t)bins * 8, hipMemcpyDeviceToHost, s));
+    std::vector<unsigned long long> slots((size_t)ffm::kEpSumSlots * ffm::kEpSumStride);
+    if (summary)
+        HIP_TRY(hipMemcpyAsync(slots.data(), e->d_ephist + ep_sum_offset(e->ephist_bins), slots.size() * 8,
+                               hipMemcpyDeviceToHost, s));
+    if (clear) HIP_TRY(clear_episode_stats(e, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (summary) {
+        unsigned long long inv_min = 0;
+        for (int j = 0; j < ffm::kEpSumSlots; j++) {
+            const unsigned long long* q = slots.data() + (size_t)j * ffm::kEpSumStride;
+            summary[0] += q[0];
+            summary[1] += q[1];
+            summary[2] += q[2];
+            inv_min = std::max(inv_min, q[3]);
+            summary[4] = std::max<uint64_t>(summary[4], q[4]);
+        }
+        summary[3] = summary[0] ? ~inv_min : 0;   // no episode yet: min reads 0
+    }
     return FFM_OK;
 }
 

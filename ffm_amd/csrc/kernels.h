@@ -43,7 +43,22 @@ struct CoreStepArgs {
     size_t scratch_stride;
     int no_step_count;        // group kernel: this launch leaves the `steps` counter alone (an env shard
                               // other than the step's first: engine.cpp, step shards)
+    // Episode log and statistics (ffm_engine_set_episode_log; episode_log.h).  All null / zero
+    // while the feature is off: ep_start != nullptr is the switch the kernels test.
+    uint32_t* ep_start;            // [E] step index that keyed each env's current placement
+    int* eplog;                    // [eplog_cap][4] {global env, episode, steps, t_end} or nullptr
+    unsigned long long* eplog_n;   // records appended (may pass eplog_cap: dropped)
+    long long eplog_cap;
+    unsigned long long* ephist;    // [ephist_bins] episodes by length (last bin: that long or longer) or nullptr
+    int ephist_bins;
+    unsigned long long* epsum;     // [kEpSumSlots][kEpSumStride] partial summaries (with ephist): count, sum of
+                                   // steps, sum of steps^2, max of ~steps (the min, inverted: zero is its empty
+                                   // value), max; an env adds to slot e % kEpSumSlots, the host sums the slots
 };
+
+// The summary is spread over slots of one 128-byte line each: a single contended word takes
+// about 100 atomic adds per us, and C2 ends about 700 episodes per step.
+constexpr int kEpSumSlots = 64, kEpSumStride = 16;
 
 // Trajectory capture of the batched ffm_core step (ffm_engine_set_trajectory_capture):
 // rows of {global env, episode, step in episode, count} + agent cells after every step.

@@ -29,6 +29,7 @@ EXPORTED = [
     "ffm_engine_get_counters", "ffm_engine_device_buffers", "ffm_engine_get_step_index",
     "ffm_engine_set_step_index", "ffm_engine_set_fused_steps", "ffm_np_expf_device",
     "ffm_engine_set_trajectory_capture", "ffm_engine_drain_trajectory",
+    "ffm_engine_set_episode_log", "ffm_engine_drain_episodes", "ffm_engine_get_episode_stats",
     "ffm_learner_create", "ffm_learner_destroy", "ffm_learner_reset", "ffm_learner_reset_envs", "ffm_learner_step",
     "ffm_learner_set_state", "ffm_learner_get_state", "ffm_learner_get_episodes",
     "ffm_learner_set_mt_state", "ffm_learner_get_mt_state", "ffm_learner_get_counters",
@@ -132,6 +133,9 @@ def load_library():
     L.ffm_engine_set_fused_steps.argtypes = [P, i32]
     L.ffm_engine_set_trajectory_capture.argtypes = [P, P, P, i32, i32, i64, P]
     L.ffm_engine_drain_trajectory.argtypes = [P, P, P, i64, C.POINTER(i64), C.POINTER(i64), P]
+    L.ffm_engine_set_episode_log.argtypes = [P, i64, i32, P]
+    L.ffm_engine_drain_episodes.argtypes = [P, P, i64, C.POINTER(i64), C.POINTER(i64), P]
+    L.ffm_engine_get_episode_stats.argtypes = [P, P, i32, P, i32, P]
     L.ffm_np_expf_device.argtypes = [P, P, i64, P]
     L.ffm_debug_launch_info.argtypes = [P, P, C.c_int]   # diagnostic, not in the ABI header
     L.ffm_debug_launch_info.restype = C.c_int
@@ -298,6 +302,8 @@ class Engine:
         d.device = int(device)
         d.envs_per_block = int(envs_per_block)
         self.device = int(device)
+        self.auto_reset = bool(auto_reset)
+        self.env_base = int(env_base)
         h = C.c_void_p()
         _check(L.ffm_engine_create(C.byref(d), C.byref(h)))
         self._h = h
@@ -384,6 +390,97 @@ class Engine:
             steps, pos = out.setdefault((env, k), ([], []))
             steps.append(st)
             pos.append(np.stack([cc // self.W, cc % self.W], axis=1))
+        return out
+
+    # -- evacuation times ------------------------------------------------------
+    def set_episode_log(self, capacity: int | None = None, hist_bins: int = 0, stream=None):
+        """Log every ended episode's length (main.py:44-56 "Simulation finished in {step}
+        steps", model/ffm_core.py:119-133 run()) on the device; see ffm_engine_set_episode_log.
+        capacity = records between drains (None: max(16 E, 4096), safe when drained every 16
+        steps; 0: no record log), hist_bins > 0 adds the histogram and summary of
+        episode_stats().  Both 0 turns the feature off."""
+        cap = max(16 * self.n_envs, 4096) if capacity is None else int(capacity)
+        _check(self._L.ffm_engine_set_episode_log(self._h, cap, int(hist_bins), _stream_handle(stream)))
+        self._eplog_cap, self._ephist_bins = cap, int(hist_bins)
+
+    def drain_episodes(self, stream=None) -> np.ndarray:
+        """Episodes ended since the last drain: int32 [n, 4] rows {global env, episode index,
+        steps, step index of the emptying step}, sorted by (env, episode)."""
+        cap = max(1, getattr(self, "_eplog_cap", 0))
+        buf = np.empty((cap, 4), np.int32)
+        n, dropped = C.c_int64(), C.c_int64()
+        _check(self._L.ffm_engine_drain_episodes(self._h, _ptr(buf), cap, C.byref(n), C.byref(dropped),
+                                                 _stream_handle(stream)))
+        if dropped.value:
+            raise RuntimeError(f"episode log overflowed: {dropped.value} records lost (drain more often)")
+        out = buf[: n.value]
+        return out[np.lexsort((out[:, 1], out[:, 0]))]
+
+    def episode_stats(self, clear: bool = False, stream=None) -> dict:
+        """The device statistics of the ended episodes' lengths: count, sum, sum_sq, min, max
+        (exact integers), mean, std (population) and hist (uint64 [hist_bins]; the last bin
+        holds every episode of hist_bins - 1 steps or more).  clear=True zeroes them after
+        the read."""
+        bins = getattr(self, "_ephist_bins", 0)
+        hist = np.zeros(bins, np.uint64)
+        s = np.zeros(5, np.uint64)
+        _check(self._L.ffm_engine_get_episode_stats(self._h, _ptr(hist) if bins else None, bins, _ptr(s),
+                                                    int(bool(clear)), _stream_handle(stream)))
+        cnt, tot, sq = int(s[0]), int(s[1]), int(s[2])
+        mean = tot / cnt if cnt else 0.0
+        var = max(0.0, (sq * cnt - tot * tot) / (cnt * cnt)) if cnt else 0.0   # exact integers up to the division
+        return {"count": cnt, "sum": tot, "sum_sq": sq, "min": int(s[3]), "max": int(s[4]), "mean": mean,
+                "std": var ** 0.5, "hist": hist}
+
+    def run_episodes(self, per_env: int = 1, max_steps: int | None = None, chunk: int = 16, stream=None) -> np.ndarray:
+        """Step until every env has logged `per_env` episodes and return their lengths, int32
+        [E, per_env] indexed by episode (counted from the last reset()): E replicas of
+        main.py's `while model.positions.shape[0] > 0: model.step()`.  Steps in calls of at
+        most `chunk` steps and drains after each; turns the record log on if it is off, and
+        discards records logged before the call (call it right after reset()).
+        Without auto_reset per_env must be 1, and the run stops when every env is empty.
+        Episodes past per_env that ended in the last chunk are discarded.  Raises
+        RuntimeError if max_steps steps did not suffice."""
+        per_env, chunk = int(per_env), int(chunk)
+        if per_env < 1 or chunk < 1:
+            raise ValueError("per_env and chunk must be >= 1")
+        if not self.auto_reset and per_env != 1:
+            raise ValueError("without auto_reset an env runs one episode: per_env must be 1")
+        if not getattr(self, "_eplog_cap", 0):
+            self.set_episode_log(capacity=max(chunk * self.n_envs, 4096), hist_bins=getattr(self, "_ephist_bins", 0),
+                                 stream=stream)
+        else:
+            try:   # records from before this run (reset() keeps the log) are not its episodes
+                self.drain_episodes(stream=stream)
+            except RuntimeError:
+                pass   # ... nor is their overflow this run's (the raising drain has emptied the log)
+        if self._eplog_cap < chunk * self.n_envs:
+            chunk = max(1, self._eplog_cap // self.n_envs)   # an env ends at most one episode per step
+        out = np.full((self.n_envs, per_env), -1, np.int32)
+        missing = self.n_envs * per_env
+        taken = 0
+        while missing:
+            n = chunk if max_steps is None else min(chunk, int(max_steps) - taken)
+            if n <= 0:
+                raise RuntimeError(f"run_episodes: {missing} episodes still running after max_steps = {max_steps}")
+            self.step(n, stream=stream)
+            taken += n
+            rec = self.drain_episodes(stream=stream)
+            late = rec[rec[:, 1] >= per_env]
+            rec = rec[rec[:, 1] < per_env]
+            e, k = rec[:, 0] - self.env_base, rec[:, 1]
+            missing -= int((out[e, k] < 0).sum())
+            out[e, k] = rec[:, 2]
+            if (out[late[:, 0] - self.env_base] < 0).any():
+                raise RuntimeError("run_episodes: an env is past episode per_env - 1 without having logged the "
+                                   "earlier ones (episodes count from the last reset(): call it right before)")
+            if missing and not self.auto_reset:
+                cnt = np.empty(self.n_envs, np.int32)
+                _check(self._L.ffm_engine_get_state(self._h, 0, self.n_envs, None, _ptr(cnt), None,
+                                                    _stream_handle(stream)))
+                if not cnt.any():
+                    raise RuntimeError(f"run_episodes: every env is empty, but {missing} logged no episode "
+                                       "(they were empty before the run, or the log was turned on after they ended)")
         return out
 
     # -- state transfer -----------------------------------------------------

@@ -174,6 +174,50 @@ int ffm_engine_set_trajectory_capture(ffm_engine* eng, const int32_t* envs, cons
 int ffm_engine_drain_trajectory(ffm_engine* eng, int32_t* meta, uint16_t* cells, int64_t cap, int64_t* n,
                                 int64_t* dropped, void* stream);
 
+/* Evacuation-time log and on-device statistics: what main.py:44-56 prints as "Simulation
+ * finished in {step} steps" and model/ffm_core.py:119-133 run() loops for, from every env
+ * without a host round trip per step.
+ *
+ * An episode of env e ends at the step after which e holds no agents, having held at least
+ * one before it: with auto_reset the step that re-places it (the event that adds 1 to
+ * episodes[e]), without it the one step that empties it.  Its length is
+ * t_end - ep_start[e] in wrapping u32 arithmetic, where ep_start[e] is the step index that
+ * keyed the env's current placement (written by ffm_engine_reset, by ffm_engine_reset_envs
+ * for the masked envs, and by the in-kernel auto-reset): a reset keyed t = 0 and an emptying
+ * step keyed t = 97 give 97, main.py's `step`.  Nothing is counted or written per step.
+ *
+ * capacity_records > 0 turns the record log on (0: off): one record of four int32 per ended
+ * episode, {global env (env_base + e), episode index k, steps, t_end}, k = episodes[e]
+ * before the increment (0-based from the last ffm_engine_reset; always 0 with auto_reset
+ * off), in no particular order.  An env ends at most one episode per step, so a capacity of
+ * 16 * n_envs is safe when the log is drained every 16 steps; records past the capacity are
+ * dropped and counted.
+ * hist_bins > 0 turns the statistics on (0: off): a histogram of u64, bin i = episodes of i
+ * steps, the last bin every episode of hist_bins - 1 steps or more, and a summary {count,
+ * sum of steps, sum of steps^2, min, max}.  They never drop anything and are integer
+ * atomics: bitwise independent of launch geometry, step shards and fused steps.
+ * Both 0 frees everything; with the feature off no kernel reads or writes anything new.
+ *
+ * ffm_engine_reset_envs is not an episode end: it logs nothing, leaves k alone and restarts
+ * the masked envs' ep_start.  ffm_engine_reset clears neither the log nor the statistics
+ * (a drain or `clear` does).  Turned on mid-run, episodes in flight count from the steps
+ * taken after the call.  ffm_engine_set_step_index inside an episode, and
+ * ffm_engine_set_state with new counts, leave the affected episodes' lengths undefined.
+ * Works with step shards, fused steps, trajectory capture and on a stream under capture
+ * (ffm_engine_step makes no host call for it).  Synchronises the stream.
+ * Philox only (MT: FFM_E_UNSUPPORTED).  Needs env_base + n_envs <= INT32_MAX. */
+int ffm_engine_set_episode_log(ffm_engine* eng, int64_t capacity_records, int32_t hist_bins, void* stream);
+/* Like ffm_learner_drain_episodes: copies min(n, capacity) records [cap][4] int32 to the
+ * host, then empties the log.  *dropped = records lost to a full log.  cap too small:
+ * FFM_E_INVALID with *n = count needed, and the log is left as it was.  Log off: *n = 0. */
+int ffm_engine_drain_episodes(ffm_engine* eng, int32_t* records, int64_t cap, int64_t* n, int64_t* dropped,
+                              void* stream);
+/* hist[bins] (bins = hist_bins) and summary[5] to the host (either may be NULL).  clear != 0
+ * zeroes them afterwards (min is restored to its empty value).  min reads 0 while count is
+ * 0; statistics off: summary reads zeros.  Synchronises the stream. */
+int ffm_engine_get_episode_stats(ffm_engine* eng, uint64_t* hist, int32_t bins, uint64_t* summary, int32_t clear,
+                                 void* stream);
+
 /* counters[4] = {agent_steps, exits, resets, steps} accumulated since create. */
 int ffm_engine_get_counters(ffm_engine* eng, uint64_t* counters, void* stream);
 int ffm_engine_device_buffers(ffm_engine* eng, ffm_device_buffers* out);
