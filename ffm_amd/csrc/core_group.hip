@@ -35,6 +35,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 
 #include "core_common.h"
 #include "kernels.h"
@@ -82,6 +83,56 @@ __host__ __device__ inline GroupCarve group_carve(int PHW, int TS, int F) {
 // the map widened to the grid's u16 codes (each wave's grids are copied from it).
 __host__ __device__ inline size_t group_shared_bytes(int PHW, int F) {
     return a16((size_t)PHW) + a16((size_t)PHW * 4) + a16((size_t)(F > 0 ? F : 1) * 2) + a16((size_t)PHW * 2);
+}
+
+// The stage image (CoreStepArgs::stage): the block-shared region above byte for byte (pads zero),
+// then one table per group size of the per-lane slot geometry, which depends on (G, lane) only.
+// A table is three arrays of 64 uint4, one entry per lane each (a 16-byte load):
+//   A  x, y, z  toff[k]: the tile float index of the lane's k-th DFF float4 slot (-1: none)
+//      w        bits 0-5   yfl: 2 bits per slot (the float4 starts / ends its row)
+//               bits 8-19  senv: 4 bits per slot (its env, 15 = none)
+//               bits 20-21 the scalar tail's cell starts / ends its row
+//               bits 24-31 the float4 index of the tile-halo word this lane clears in the
+//                          prologue (255: none)
+//   B  lo[0], ro[0], lo[1], ro[1]: the tile float index of slot k's left and right neighbour
+//      in its row, toff[k] - 1 and toff[k] + 4, or 0 (a zero word of the halo) across the
+//      map's edge and for a missing slot
+//   C  the same two of the scalar tail's cell, then lo[2], ro[2]
+constexpr int kGeomWords = 12;
+constexpr int kGeomTableBytes = 64 * kGeomWords * 4;
+
+template <int H, int W, int G>
+void group_lane_geom(int lane, int32_t (&w)[kGeomWords]) {
+    constexpr int HW = H * W, TS = lane_tile_floats(H, W), Q4 = HW / 4, Q = G * Q4;
+    constexpr int NS = (Q + 63) / 64, NSF = Q / 64, HQ = (4 + W) / 4;
+    static_assert(NS <= 3 && (4 + W) % 4 == 0 && TS % 4 == 0 && G * 2 * HQ <= 64 && G * TS / 4 <= 255,
+                  "geometry table entry");
+    uint32_t yfl = 0, senv = 0, tail = 0;
+    int lo[3] = {0, 0, 0}, ro[3] = {0, 0, 0}, tlo = 0, tro = 0;
+    for (int k = 0; k < 3; k++) w[k] = -1;
+    for (int k = 0; k < NS; k++) {
+        const int q = k * 64 + lane;
+        const int s = q / Q4, c = 4 * (q - s * Q4), y = c % W;
+        w[k] = q < Q ? s * TS + 4 + W + c : -1;
+        yfl |= (q < Q && y == 0 ? 1u : 0u) << (2 * k);
+        yfl |= (q < Q && y == W - 4 ? 2u : 0u) << (2 * k);
+        senv |= (uint32_t)(q < Q ? s : 15) << (4 * k);
+        lo[k] = q < Q && y != 0 ? w[k] - 1 : 0;
+        ro[k] = q < Q && y != W - 4 ? w[k] + 4 : 0;
+    }
+    if (Q % 64 != 0 && (Q % 64) * 4 == 64) {   // SCALAR_TAIL's cell (the kernel uses it with NB == 4)
+        const int q = 4 * 64 * NSF + lane;
+        const int s = q / HW, c = q - s * HW, y = c % W, off = s * TS + 4 + W + c;
+        tail = (y == 0 ? 1u : 0u) | (y == W - 1 ? 2u : 0u);
+        tlo = y != 0 ? off - 1 : 0;
+        tro = y != W - 1 ? off + 1 : 0;
+    }
+    // the halo of env s's tile: its first and last HQ float4s (lane_tile_floats)
+    const int s = lane / (2 * HQ), j = lane % (2 * HQ);
+    const uint32_t halo = lane < G * 2 * HQ ? (uint32_t)(s * (TS / 4) + (j < HQ ? j : TS / 4 - 2 * HQ + j)) : 255u;
+    w[3] = (int32_t)(yfl | (senv << 8) | (tail << 20) | (halo << 24));
+    w[4] = lo[0]; w[5] = ro[0]; w[6] = lo[1]; w[7] = ro[1];
+    w[8] = tlo; w[9] = tro; w[10] = lo[2]; w[11] = ro[2];
 }
 
 // Packed per-chunk state (one VGPR each):
@@ -141,6 +192,15 @@ __device__ __forceinline__ int cs_xp1(uint32_t v) { return (int)(v >> 25); }
 #define FFM_GROUP_WAVES 6   // minimum waves per SIMD asked of the register allocator (G = 4 needs 71 VGPRs; the grid holds 6 per SIMD)
 #endif
 
+#ifndef FFM_GROUP_G
+#define FFM_GROUP_G 4
+#endif
+constexpr int kGroupG = FFM_GROUP_G;   // envs per group at large E
+#ifndef FFM_GROUP_G_SMALL
+#define FFM_GROUP_G_SMALL 2
+#endif
+constexpr int kGroupGSmall = FFM_GROUP_G_SMALL;   // envs per group when the large-E groups fill under half the waves
+
 // EPL: the episode log (episode_log.h) as a kernel of its own, as KD1 is (group_op): behind a
 // runtime pointer its code costs the step 4 VGPRs with the log off.
 template <int NB, int HT, int WT, int G, bool KD1, bool EPL>
@@ -166,11 +226,10 @@ void core_group_kernel(CoreStepArgs a) {
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 
     const GroupCarve cv = group_carve<G>(PHW, TS, a.F);
-    uint8_t* pmap = smem;
-    float* psff = reinterpret_cast<float*>(smem + a16((size_t)PHW));
-    uint16_t* pfree = reinterpret_cast<uint16_t*>(smem + a16((size_t)PHW) + a16((size_t)PHW * 4));
-    uint16_t* pmap16 = reinterpret_cast<uint16_t*>(smem + a16((size_t)PHW) + a16((size_t)PHW * 4) +
-                                                   a16((size_t)(a.F > 0 ? a.F : 1) * 2));
+    // block-shared (group_shared_bytes): the map and the widened map are in the image too, but
+    // the kernel reads only the SFF term and the free list from LDS
+    const float* psff = reinterpret_cast<const float*>(smem + a16((size_t)PHW));
+    const uint16_t* pfree = reinterpret_cast<const uint16_t*>(smem + a16((size_t)PHW) + a16((size_t)PHW * 4));
     unsigned char* wbase = smem + group_shared_bytes(PHW, a.F) + (size_t)wv * cv.per_wave;
     uint16_t* const grid = reinterpret_cast<uint16_t*>(wbase + cv.grid);
     float* const tile = reinterpret_cast<float*>(wbase + cv.tile);
@@ -183,18 +242,37 @@ void core_group_kernel(CoreStepArgs a) {
     const int kDummy16 = (int)((cv.dummy - cv.grid) / 2);    // grid index of the dummy word
     const int kDummy32 = (int)((cv.dummy - cv.words) / 4);   // words index of the dummy word
 
-    // The lane's DFF float4 slots: q = 64 k + lane of the group's G * HW cells,
-    // env q / Q4, cell 4 (q % Q4) of that env.
+    // The stage image (kernels.h): one resource over its block-shared part and both geometry tables.
+    static_assert(G == kGroupG || G == kGroupGSmall, "a geometry table per built group size");
+    const int sq4 = a.stage_q4;
+    const __amdgpu_buffer_rsrc_t rS = pair_rsrc(a.stage, sq4 * 16 + 2 * kGeomTableBytes);
+    // The lane's DFF float4 slots: q = 64 k + lane of the group's G * HW cells, env q / Q4,
+    // cell 4 (q % Q4) of that env.  Their tile offsets and flags depend on (G, lane) only and
+    // come from the image's table (group_lane_geom): 16-byte loads of the lane's entries.
+    const int gtab = sq4 * 16 + (G == kGroupG ? kGeomTableBytes : 0);
+    auto geom = [&](int j) {   // array j of the table: the lane's entry
+        return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rS, lane * 16 + j * 1024, gtab, 0));
+    };
+    const uint4 gw = geom(0);
+    static_assert(NS <= 3, "geometry table entry");
     int toff[NS];
-    uint32_t yfl = 0, senv = 0;
 #pragma unroll
-    for (int k = 0; k < NS; k++) {
-        const int q = k * 64 + lane;
-        const int s = q / Q4, c = 4 * (q - s * Q4), y = c % W;
-        toff[k] = q < Q ? s * TS + 4 + W + c : -1;
-        yfl |= (q < Q && y == 0 ? 1u : 0u) << (2 * k);
-        yfl |= (q < Q && y == W - 4 ? 2u : 0u) << (2 * k);
-        senv |= (uint32_t)(q < Q ? s : 15) << (4 * k);
+    for (int k = 0; k < NS; k++) toff[k] = (int)(k == 0 ? gw.x : k == 1 ? gw.y : gw.z);
+    // yfl at bit 0 (2 bits per slot), senv at bit 8 (4 per slot), the halo word at bit 24
+    const uint32_t geo = gw.w;
+    // Neumann: the stencil's left / right neighbours by their own offsets (0: the halo's zero
+    // word), so the float4 slots test and hold no edge flag in the loop.  Moore keeps the flags (yfl).
+    int lo[NS], ro[NS];
+#pragma unroll
+    for (int k = 0; k < NS; k++) lo[k] = ro[k] = 0;
+    if (NB == 4) {
+        const uint4 gb = geom(1);
+        lo[0] = (int)gb.x; ro[0] = (int)gb.y;
+        if (NS > 1) { lo[1] = (int)gb.z; ro[1] = (int)gb.w; }
+        if (NS > 2 && !SCALAR_TAIL) {
+            const uint4 gc = geom(2);
+            lo[2] = (int)gc.z; ro[2] = (int)gc.w;
+        }
     }
 
     const long long E = a.E;                   // host-checked: (E + 7) * HW * 4 < 2^31
@@ -255,23 +333,32 @@ void core_group_kernel(CoreStepArgs a) {
     load(g < ngroups ? g : -1, cur);
 
     if (LAD >= 1) {
-    for (int i = threadIdx.x; i < PHW; i += 256) {
-        const uint8_t mv = a.pmap[i];
-        pmap[i] = mv;
-        pmap16[i] = mv;
-        psff[i] = a.kS32 * reinterpret_cast<const float*>(a.psff)[i];   // the score's SFF term
-    }
-    for (int i = threadIdx.x; i < a.F; i += 256) pfree[i] = a.free_padded[i];
-    static_assert((G * TS) % 4 == 0 && PHW % 2 == 0, "16-B tile clears, 4-B grid copies");
-    for (int i = lane; i < G * TS / 4; i += 64) reinterpret_cast<float4*>(tile)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (lane < kGroupPendWords) pend[lane] = 0u;
-    __syncthreads();
-    // every env's grid starts as the map: dword copies of the widened map, no per-cell modulo
+    // Block-shared region: the image's first sq4 float4s, one 16-byte load and LDS store per
+    // thread (the host checks sq4 <= 256).  The map, f32(-k_S) * SFF, the free list and the
+    // widened map are engine constants: nothing is recomputed per launch.
+    if ((int)threadIdx.x < sq4)
+        reinterpret_cast<uint4*>(smem)[threadIdx.x] = __builtin_bit_cast(
+            uint4, __builtin_amdgcn_raw_buffer_load_b128(rS, (int)threadIdx.x * 16, 0, 0));
+    // Every env's grid starts as the map: the widened map straight from the image (8 bytes per
+    // lane, G LDS stores), so the wave's own state does not wait for the block's.
+    static_assert((PHW * 2) % 8 == 0 && PHW * 2 / 8 <= 64, "8-B grid copies, one per lane");
+    if (lane < PHW * 2 / 8) {
+        const int pm16 = (int)(a16((size_t)PHW) + a16((size_t)PHW * 4) + a16((size_t)(a.F > 0 ? a.F : 1) * 2));
+        const auto mw = __builtin_amdgcn_raw_buffer_load_b64(rS, lane * 8, pm16, 0);
 #pragma unroll
-    for (int s = 0; s < G; s++)
-        for (int i = lane; i < PHW / 2; i += 64)
-            reinterpret_cast<uint32_t*>(grid)[s * (PHW / 2) + i] = reinterpret_cast<const uint32_t*>(pmap16)[i];
-    wave_sync();
+        for (int s = 0; s < G; s++)
+            *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(grid) + s * (PHW * 2) + lane * 8) =
+                __builtin_bit_cast(uint2, mw);
+    }
+    // Only the tiles' halos are cleared (the zero rows above and below the map with the 4 floats
+    // before and after them, G * 8 float4s: one store).  The interior needs no clear: every
+    // iteration stages all NS slots of its group before anything reads the tile, a partial
+    // group's loads return the arrays' zeroed padding, and loads past the last group go through
+    // the empty resource and return zero.  Nothing ever writes the halo.
+    if ((geo >> 24) != 255u) reinterpret_cast<float4*>(tile)[geo >> 24] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (lane < kGroupPendWords) pend[lane] = 0u;
+    // the block-shared region is first read by decide (the SFF term) and by the placement tail
+    __syncthreads();
     }
 
     unsigned c_steps = 0, c_exits = 0, c_resets = 0;
@@ -513,12 +600,15 @@ void core_group_kernel(CoreStepArgs a) {
         // then the DFF stores (an env reset this step starts its next episode at zero) ----
         if (SCALAR_TAIL) {     // the last, partial float4 slot as one cell per lane (all lanes busy)
             const int q = 4 * 64 * NSF + lane;                 // the group's cell
-            const int s = q / HW, c = q - s * HW, y = c % W;
-            const float* p = tile + s * TS + 4 + W + c;
+            // the 64 cells lie in one env (ts), so the tile offset is a constant plus the lane
+            constexpr int ts = 4 * 64 * NSF / HW, tc = 4 * 64 * NSF - ts * HW;
+            static_assert(!SCALAR_TAIL || (4 * 64 * NSF + 63) / HW == ts, "the scalar tail spans envs");
+            const float* p = tile + (ts * TS + 4 + W + tc) + lane;
             // p[-1] / p[1] lie inside the tile at the map's edges too (the zero rows above and
-            // below): read them unconditionally, select the edge's zero (no exec-mask branch)
+            // below): read them unconditionally, select the edge's zero (no exec-mask branch; two
+            // more offsets from the table instead cost the kernel two VGPRs)
             const float m0 = p[0], mu = p[-W], md = p[W], pl = p[-1], pr = p[1];
-            const float ml = y == 0 ? 0.0f : pl, mr = y == W - 1 ? 0.0f : pr;
+            const float ml = (geo & (1u << 20)) ? 0.0f : pl, mr = (geo & (2u << 20)) ? 0.0f : pr;
             // B = c0 * D per operand, then A = B + sum c1 * B[nb] in neighbour order (:106-117)
             const float b0 = a.c0 * m0, bu = a.c0 * mu, bd = a.c0 * md, bl = a.c0 * ml, br = a.c0 * mr;
             float acc = b0;
@@ -527,14 +617,14 @@ void core_group_kernel(CoreStepArgs a) {
             acc = acc + a.c1 * bl;
             acc = acc + a.c1 * br;
             float o = acc < 1e-4f ? 0.0f : acc;
-            if (rsm && ((rsm >> s) & 1ull)) o = 0.0f;   // rsm wave-uniform and rare
+            if (rsm && ((rsm >> ts) & 1ull)) o = 0.0f;   // rsm wave-uniform and rare
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, o), rD, q * 4, e0 * HW * 4, 0);
         }
 #pragma unroll
         for (int k = 0; k < (SCALAR_TAIL ? NSF : NS); k++) {
             const int tb = toff[k];
             if (k >= NSF && tb < 0) continue;
-            const bool yl = ((yfl >> (2 * k)) & 1u) != 0u, yr = ((yfl >> (2 * k)) & 2u) != 0u;
+            const bool yl = ((geo >> (2 * k)) & 1u) != 0u, yr = ((geo >> (2 * k)) & 2u) != 0u;
             const float* p = tile + tb;
             float b[3][6];   // rows dx = -1..1, columns -1..4 (B values)
 #pragma unroll
@@ -543,8 +633,8 @@ void core_group_kernel(CoreStepArgs a) {
                 b[dx + 1][1] = a.c0 * u.x; b[dx + 1][2] = a.c0 * u.y;
                 b[dx + 1][3] = a.c0 * u.z; b[dx + 1][4] = a.c0 * u.w;
                 if (NB == 4 && dx != 0) continue;
-                b[dx + 1][0] = a.c0 * tile[yl ? 0 : tb + dx * W - 1];   // tile[0] == 0
-                b[dx + 1][5] = a.c0 * tile[yr ? 0 : tb + dx * W + 4];
+                b[dx + 1][0] = a.c0 * tile[NB == 4 ? lo[k] : yl ? 0 : tb + dx * W - 1];   // tile[0] == 0
+                b[dx + 1][5] = a.c0 * tile[NB == 4 ? ro[k] : yr ? 0 : tb + dx * W + 4];
             }
             float o[4];
 #pragma unroll
@@ -559,7 +649,7 @@ void core_group_kernel(CoreStepArgs a) {
             }
             float4 out = make_float4(o[0], o[1], o[2], o[3]);
             if (rsm) {   // wave-uniform, rare: an env re-placed this step starts its next episode at zero
-                if ((rsm >> ((senv >> (4 * k)) & 15u)) & 1ull) out = make_float4(0.f, 0.f, 0.f, 0.f);
+                if ((rsm >> ((geo >> (8 + 4 * k)) & 15u)) & 1ull) out = make_float4(0.f, 0.f, 0.f, 0.f);
             }
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, out),
                                                    rD, (k * 64 + lane) * 16, e0 * HW * 4, 0);
@@ -569,16 +659,20 @@ void core_group_kernel(CoreStepArgs a) {
     }
 
     // ---- deferred auto-reset placements ------------------------------
-    wave_sync();
-    for (int w = 0; w < (LAD >= 1 ? kGroupPendWords : 0); w++) {   // ladder rung 0: pend never initialised
+    // c_resets (wave-uniform) counts the bits set in pend: most waves re-place no env and skip
+    // the tail with its setup (the placement's loop invariants)
+    if (c_resets) wave_sync();
+    for (int w = 0; w < (LAD >= 1 && c_resets ? kGroupPendWords : 0); w++) {   // ladder rung 0: pend never initialised
         uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)pend[w]);
         while (m) {
             const int bit = w * 32 + __builtin_ctz(m);
             m &= m - 1u;
             const long long e = (long long)(g_first + (bit >> 3) * wstride) * G + (bit & 7);
-            wave_reset_env(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane);
+            // at most (H - 2) * (W - 2) cells are free: the placement's small-list path only
+            static_assert((H - 2) * (W - 2) <= 128, "wave_reset_env<.., SMALL>");
+            wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane);
             if (FFM_GROUP_ABLATE & 1)   // diagnostic: the same placement again (identical result)
-                wave_reset_env(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane);
+                wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane);
         }
     }
 
@@ -591,15 +685,6 @@ void core_group_kernel(CoreStepArgs a) {
     }
 }
 
-#ifndef FFM_GROUP_G
-#define FFM_GROUP_G 4
-#endif
-constexpr int kGroupG = FFM_GROUP_G;   // envs per group at large E
-#ifndef FFM_GROUP_G_SMALL
-#define FFM_GROUP_G_SMALL 2
-#endif
-constexpr int kGroupGSmall = FFM_GROUP_G_SMALL;   // envs per group when the large-E groups fill under half the waves
-
 size_t core_group_smem_bytes(int H, int W, int F, int waves, int G) {
     const int PHW = (H + 2) * (W + 2);
     const size_t per_wave = G == kGroupGSmall ? group_carve<kGroupGSmall>(PHW, lane_tile_floats(H, W), F).per_wave
@@ -610,6 +695,44 @@ size_t core_group_smem_bytes(int H, int W, int F, int waves, int G) {
 bool core_group_supported(int H, int W) { return H == 12 && W == 12; }
 
 int core_group_max_iters() { return kGroupMaxIters; }
+
+int core_group_stage_q4(int H, int W, int F) { return (int)(group_shared_bytes((H + 2) * (W + 2), F) / 16); }
+
+size_t core_group_stage_bytes(int H, int W, int F) {
+    return group_shared_bytes((H + 2) * (W + 2), F) + 2 * (size_t)kGeomTableBytes;
+}
+
+// The image on the host.  The SFF term is the one f32 product the kernel used to stage per launch,
+// f32(-k_S) * SFF: a single IEEE multiply (this file is built without contraction), so the bits
+// are the device's.
+void core_group_stage_build(int H, int W, int F, const uint8_t* pmap, const float* psff, float kS32,
+                            const uint16_t* free_padded, unsigned char* out) {
+    const int PHW = (H + 2) * (W + 2);
+    std::memset(out, 0, core_group_stage_bytes(H, W, F));
+    unsigned char* p = out;
+    std::memcpy(p, pmap, (size_t)PHW);
+    p += a16((size_t)PHW);
+    for (int i = 0; i < PHW; i++) {
+        const float v = kS32 * psff[i];
+        std::memcpy(p + 4 * (size_t)i, &v, 4);
+    }
+    p += a16((size_t)PHW * 4);
+    if (F > 0) std::memcpy(p, free_padded, (size_t)F * 2);
+    p += a16((size_t)(F > 0 ? F : 1) * 2);
+    for (int i = 0; i < PHW; i++) {
+        const uint16_t v = pmap[i];
+        std::memcpy(p + 2 * (size_t)i, &v, 2);
+    }
+    p += a16((size_t)PHW * 2);
+    if (!core_group_supported(H, W)) return;
+    for (int lane = 0; lane < 64; lane++) {
+        int32_t w[kGeomWords];
+        group_lane_geom<12, 12, kGroupGSmall>(lane, w);
+        for (int j = 0; j < kGeomWords / 4; j++) std::memcpy(p + j * 1024 + lane * 16, w + 4 * j, 16);
+        group_lane_geom<12, 12, kGroupG>(lane, w);
+        for (int j = 0; j < kGeomWords / 4; j++) std::memcpy(p + kGeomTableBytes + j * 1024 + lane * 16, w + 4 * j, 16);
+    }
+}
 
 // KD1: k_D == 1 (the drivers' setting), where k_D * DFF is DFF itself: a kernel of its own
 // rather than a runtime flag, which the register allocator would keep (and spill) all launch.
@@ -626,6 +749,9 @@ static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int
     const long long groups = (a.E + G - 1) / G;
     if (a.H != 12 || a.W != 12 || a.A > 32 || (groups + (long long)blocks * 4 - 1) / ((long long)blocks * 4) > kGroupMaxIters)
         return hipErrorInvalidConfiguration;   // shapes the kernel and its grid assume
+    // the prologue copies the image's block-shared part with one 16-byte load per thread
+    if (!a.stage || a.stage_q4 != core_group_stage_q4(a.H, a.W, a.F) || a.stage_q4 > 256)
+        return hipErrorInvalidConfiguration;
     if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
     else core_group_kernel<NB, 12, 12, G, KD1, false><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
     return hipGetLastError();

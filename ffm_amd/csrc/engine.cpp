@@ -65,6 +65,9 @@ struct ffm_engine {
     void* d_sff = nullptr;       // padded SFF
     uint16_t* d_free = nullptr;
     uint16_t* d_free_padded = nullptr;
+    unsigned char* d_stage = nullptr;   // group kernel: the stage image (kernels.h), engine constants
+    size_t stage_bytes = 0;
+    int stage_q4 = 0;
     uint16_t* d_pos = nullptr;
     int32_t* d_cnt = nullptr;
     float* d_dff = nullptr;
@@ -153,6 +156,7 @@ static void release(ffm_engine* e) {
     (void)hipFree(e->d_sff);
     (void)hipFree(e->d_free);
     (void)hipFree(e->d_free_padded);
+    (void)hipFree(e->d_stage);
     (void)hipFree(e->d_pos);
     (void)hipFree(e->d_cnt);
     (void)hipFree(e->d_dff);
@@ -289,6 +293,11 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
     ALLOC(e->d_sff, sff_bytes);
     ALLOC(e->d_free, std::max<size_t>(1, fl.size()) * 2);
     ALLOC(e->d_free_padded, std::max<size_t>(1, fl.size()) * 2);
+    if (e->group) {
+        e->stage_bytes = ffm::core_group_stage_bytes(H, W, e->F);
+        e->stage_q4 = ffm::core_group_stage_q4(H, W, e->F);
+        ALLOC(e->d_stage, e->stage_bytes);
+    }
     // pos / cnt / DFF hold whole groups of 8 envs (zeroed padding beyond n_envs): the group kernel
     // reads and writes a partial last group through whole-array buffer resources (core_group.hip)
     const size_t Ep = (E + 7) & ~(size_t)7;
@@ -440,6 +449,14 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
         for (size_t i = 0; i < fl.size(); i++) fp[i] = (uint16_t)((fl[i] / W + 1) * PW + fl[i] % W + 1);
         he = hipMemcpy(e->d_free_padded, fp.data(), fp.size() * 2, hipMemcpyHostToDevice);
     }
+    if (he == hipSuccess && e->group) {
+        // the map, the SFF term, k_S and the free list have no setter: the image is final
+        std::vector<uint16_t> fp(fl.size());
+        for (size_t i = 0; i < fl.size(); i++) fp[i] = (uint16_t)((fl[i] / W + 1) * PW + fl[i] % W + 1);
+        std::vector<unsigned char> img(e->stage_bytes);
+        ffm::core_group_stage_build(H, W, e->F, pmap.data(), psff32.data(), e->kS32, fp.data(), img.data());
+        he = hipMemcpy(e->d_stage, img.data(), img.size(), hipMemcpyHostToDevice);
+    }
     if (he == hipSuccess) he = hipMemset(e->d_pos, 0xFF, pos_bytes);
     if (he == hipSuccess) he = hipMemset(e->d_cnt, 0, Ep * 4);
     if (he == hipSuccess) he = hipMemset(e->d_dff, 0, Ep * HW * 4);
@@ -492,6 +509,8 @@ static ffm::CoreStepArgs make_args(ffm_engine* e) {
     a.free_list = e->d_free;
     a.free_padded = e->d_free_padded;
     a.F = e->F;
+    a.stage = e->d_stage;
+    a.stage_q4 = e->stage_q4;
     a.mt_np = e->d_mt_np;
     a.mt_py = e->d_mt_py;
     a.dbg = e->d_dbg;
@@ -942,6 +961,17 @@ int ffm_engine_set_step_index(ffm_engine* e, uint32_t t) {
 int ffm_debug_read(ffm_engine* e, uint64_t* out, int n) {
     if (!e || !out || n < 0 || n > 16) return fail(FFM_E_INVALID, "bad args");
     HIP_TRY(hipMemcpy(out, e->d_dbg, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return FFM_OK;
+}
+
+// Diagnostic: the group kernel's stage image (kernels.h), copied to the host.  *n gets its size in
+// bytes (0 for engines of the other kernels); the copy is made when `out` holds that many.
+int ffm_debug_stage_image(ffm_engine* e, void* out, int64_t cap, int64_t* n) {
+    if (!e || !n || cap < 0) return fail(FFM_E_INVALID, "bad args");
+    *n = (int64_t)e->stage_bytes;
+    if (!out || e->stage_bytes == 0) return FFM_OK;
+    if (cap < (int64_t)e->stage_bytes) return fail(FFM_E_INVALID, "stage_image: buffer too small (*n holds the size)");
+    HIP_TRY(hipMemcpy(out, e->d_stage, e->stage_bytes, hipMemcpyDeviceToHost));
     return FFM_OK;
 }
 

@@ -43,6 +43,11 @@ struct CoreStepArgs {
     size_t scratch_stride;
     int no_step_count;        // group kernel: this launch leaves the `steps` counter alone (an env shard
                               // other than the step's first: engine.cpp, step shards)
+    // Group kernel: the engine-constant stage image (core_group_stage_build; 16-B aligned).  Its
+    // first stage_q4 float4s are the block-shared LDS region byte for byte; the per-lane geometry
+    // tables of both group sizes follow.  Built once at create: nothing in it has a setter.
+    const void* stage;
+    int stage_q4;
     // Episode log and statistics (ffm_engine_set_episode_log; episode_log.h).  All null / zero
     // while the feature is off: ep_start != nullptr is the switch the kernels test.
     uint32_t* ep_start;            // [E] step index that keyed each env's current placement
@@ -84,6 +89,13 @@ int core_lane_max_pairs_per_wave();
 size_t core_group_smem_bytes(int H, int W, int F, int waves, int G = 4);
 bool core_group_supported(int H, int W);
 int core_group_max_iters();
+// The stage image of the group kernel (CoreStepArgs::stage): its size, the float4s of its
+// block-shared part, and the host-side build from the padded map, the padded f32 SFF, f32(-k_S)
+// and the padded free list.
+size_t core_group_stage_bytes(int H, int W, int F);
+int core_group_stage_q4(int H, int W, int F);
+void core_group_stage_build(int H, int W, int F, const uint8_t* pmap, const float* psff, float kS32,
+                            const uint16_t* free_padded, unsigned char* out);
 int core_group_pick_envs(const CoreStepArgs& a, int nb, long long E, int cus);   // envs per group (2 or 4)
 hipError_t launch_core_group(const CoreStepArgs& a, int nb, int blocks, hipStream_t s, int G);
 int core_group_blocks_per_cu(const CoreStepArgs& a, int nb, int G);

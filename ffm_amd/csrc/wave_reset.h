@@ -19,11 +19,16 @@ __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, i
 // rarely-taken branch sits inside the step loop and would otherwise set the
 // kernel's VGPR peak.  Larger F: threshold the keys into an LDS candidate list
 // first (about 2N + 16 survive).
+// PWK > 0: the padded row width as a constant (a kernel built for one map width).  SMALL: the
+// caller's maps have at most 128 free cells, so the threshold path below is not built -- its
+// divisions by F and PW are loop invariants the compiler otherwise sets up in every wave of a
+// kernel that holds this call in a loop, whether or not an env is re-placed.
+template <int PWK = 0, bool SMALL = false>
 __device__ inline void wave_reset_env(const CoreStepArgs& a, uint32_t genv, unsigned long long* keys, const uint16_t* fl,
                                uint16_t* gpos, int lane) {
-    const int PW = a.W + 2;
+    const int PW = PWK > 0 ? PWK : a.W + 2;
     const int F = a.F, N = a.N;
-    if (F <= 128) {
+    if (SMALL || F <= 128) {
         // lane holds keys j0 = lane and j1 = lane + 64 and ranks both in one pass over
         // 16-B broadcast reads of the key list (two keys per read; keys is 16-B aligned)
         const int j0 = lane, j1 = lane + 64;

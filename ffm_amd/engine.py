@@ -30,6 +30,7 @@ EXPORTED = [
     "ffm_engine_set_step_index", "ffm_engine_set_fused_steps", "ffm_np_expf_device",
     "ffm_engine_set_trajectory_capture", "ffm_engine_drain_trajectory",
     "ffm_engine_set_episode_log", "ffm_engine_drain_episodes", "ffm_engine_get_episode_stats",
+    "ffm_debug_stage_image",
     "ffm_learner_create", "ffm_learner_destroy", "ffm_learner_reset", "ffm_learner_reset_envs", "ffm_learner_step",
     "ffm_learner_set_state", "ffm_learner_get_state", "ffm_learner_get_episodes",
     "ffm_learner_set_mt_state", "ffm_learner_get_mt_state", "ffm_learner_get_counters",
@@ -137,6 +138,7 @@ def load_library():
     L.ffm_engine_drain_episodes.argtypes = [P, P, i64, C.POINTER(i64), C.POINTER(i64), P]
     L.ffm_engine_get_episode_stats.argtypes = [P, P, i32, P, i32, P]
     L.ffm_np_expf_device.argtypes = [P, P, i64, P]
+    L.ffm_debug_stage_image.argtypes = [P, P, i64, C.POINTER(i64)]
     L.ffm_debug_launch_info.argtypes = [P, P, C.c_int]   # diagnostic, not in the ABI header
     L.ffm_debug_launch_info.restype = C.c_int
     L.ffm_learner_create.argtypes = [C.POINTER(EngineDesc), C.POINTER(LearnDesc), C.POINTER(P)]
@@ -570,6 +572,16 @@ class Engine:
         return {"kernel": ("group", "lane", "wave", "block", "block_scratch")[int(v[0])], "group_g": int(v[1]),
                 "blocks": int(v[2]), "K": int(v[3]), "block_size": int(v[4]), "multi": bool(v[5]),
                 "multi_blocks": int(v[6]), "step_shards": int(v[7]), "shard_blocks": int(v[8])}
+
+    def stage_image(self) -> np.ndarray:
+        """The group kernel's engine-constant stage image as bytes (diagnostic,
+        ffm_debug_stage_image); empty for engines of the other kernels."""
+        n = C.c_int64()
+        _check(self._L.ffm_debug_stage_image(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint8)
+        if n.value:
+            _check(self._L.ffm_debug_stage_image(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
 
     @property
     def step_index(self) -> int:

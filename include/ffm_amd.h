@@ -512,6 +512,15 @@ int ffm_learner_set_step_index(ffm_learner* l, uint32_t t);
 /* y[i] = NumPy-exact float32 exp(x[i]) computed on the device; device pointers. */
 int ffm_np_expf_device(const float* x, float* y, int64_t n, void* stream);
 
+/* ---- diagnostics ------------------------------------------------------ */
+/* The engine-constant stage image of the group step kernel (12x12 rooms, <= 32 agents), copied
+ * to the host: the bytes every workgroup copies into its shared memory (the padded map as u8,
+ * f32(-k_S) * SFF, the padded free list as u16, the padded map as u16; each region padded with
+ * zeros to 16 bytes), then the per-lane geometry tables of the two group sizes.  *n receives
+ * the size in bytes (0: the engine steps with another kernel); the copy is made when out is
+ * not NULL and cap >= *n. */
+int ffm_debug_stage_image(ffm_engine* eng, void* out, int64_t cap, int64_t* n);
+
 #ifdef __cplusplus
 }
 #endif
