@@ -145,6 +145,79 @@ __device__ __forceinline__ int cs_s(uint32_t v) { return (int)((v >> 21) & 7u); 
 __device__ __forceinline__ bool cs_live(uint32_t v) { return ((v >> 24) & 1u) != 0u; }
 __device__ __forceinline__ int cs_xp1(uint32_t v) { return (int)(v >> 25); }
 
+__device__ __forceinline__ float lane_f32(float x, int l) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l));
+}
+
+// decide(), exact pass (lane_decide_exact, Neumann) for the chunk's pending lanes `pend`, one
+// agent at a time across the wave: candidate k (0..3 neighbour, 4 stay) is evaluated on lane k,
+// so the score, NumPy's exp and the f32 divide run once per candidate and side by side, and
+// nothing is re-read from LDS.  Every rounding is the serial path's, in its order: the max,
+// the f32 sum from -0 and the f64 cumsum are folded over the valid candidates in candidate
+// order from the lanes' values (wave-uniform operands, dependent adds).  Called in wave-uniform
+// control flow with all lanes active; csv is the chunk's cs word, wx / wy the decide draw.
+template <int W, int PHW, int TS>
+__device__ __forceinline__ uint32_t group_exact_coop(unsigned long long pend, uint32_t slot, uint32_t csv, uint32_t wx,
+                                                     uint32_t wy, const uint16_t* grid, const float* psff,
+                                                     const float* tile, float kD, int lane) {
+    constexpr int NB = 4, PW = W + 2;
+    while (pend) {
+        const int L = __builtin_ctzll(pend);   // lowest pending lane first
+        pend &= pend - 1ull;
+        // candidate `lane`: its grid and tile offsets from the agent's cell (nb_dx / nb_dy<4>).
+        // Opaque, so they are formed here, per pending agent: as loop invariants they are hoisted
+        // out of the group loop and held through every iteration (G = 4: 78 VGPRs against 73).
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int off = ln == 0 ? -PW : ln == 1 ? PW : ln == 2 ? -1 : ln == 3 ? 1 : 0;
+        const int doff = ln == 0 ? -W : ln == 1 ? W : ln == 2 ? -1 : ln == 3 ? 1 : 0;
+        const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)csv, L);
+        const int pp = cs_pp(v), s = cs_s(v), dd0 = 3 - 2 * cs_xp1(v);
+        const int cell = pp + off;   // lanes past the candidates: the agent's own cell
+        const uint32_t g = grid[s * PHW + cell];
+        // the valid candidates as a wave-uniform mask: free or exit neighbours, and the stay
+        const unsigned vm = ((unsigned)__ballot(g == 0u || g == 3u) & ((1u << NB) - 1u)) | (1u << NB);   // :52-60
+        const float sa = psff[cell];
+        const float sb = kD * tile[s * TS + pp + dd0 + doff];
+        const float sc = sa + sb;                                                      // :77
+        float mx = -__builtin_inff();
+#pragma unroll
+        for (int k = 0; k <= NB; k++) {
+            const float sk = lane_f32(sc, k);
+            mx = (((vm >> k) & 1u) && sk > mx) ? sk : mx;                              // :78
+        }
+        const float e = np_expf(sc - mx);                                              // :80
+        float sum = -0.0f;                                                             // add.reduce, < 8 terms: left fold
+#pragma unroll
+        for (int k = 0; k <= NB; k++) {
+            const float t = sum + lane_f32(e, k);
+            sum = ((vm >> k) & 1u) ? t : sum;                                          // :81
+        }
+        const float p = e / sum;                                                       // :83
+        // the f64 cumsum in choice: every lane folds the same terms, lane k through candidate k
+        // (its mask is vm up to bit k), so lane NB ends with the total; the masks derive from
+        // vm, not from the lane alone, and so are not held in SGPRs across the loop
+        const unsigned vmk = vm & ((2u << (ln & 7)) - 1u);
+        double run = 0.0;
+#pragma unroll
+        for (int k = 0; k <= NB; k++) {
+            const double t = run + (double)lane_f32(p, k);
+            run = ((vmk >> k) & 1u) ? t : run;
+        }
+        const unsigned long long rb = __builtin_bit_cast(unsigned long long, run);
+        const double last = __builtin_bit_cast(
+            double, ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(rb >> 32), NB) << 32) |
+                        (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)rb, NB));
+        const double inv = 1.0 / last;
+        const double u = u53((uint32_t)__builtin_amdgcn_readlane((int)wx, L),
+                             (uint32_t)__builtin_amdgcn_readlane((int)wy, L));
+        const unsigned gt = (unsigned)__ballot(cdf_gt(run, last, inv, u)) & vm & ((1u << NB) - 1u);
+        const uint32_t pick = gt ? (uint32_t)__builtin_ctz(gt) : (uint32_t)NB;         // cdf[-1] == 1 > u
+        slot = lane == L ? pick : slot;
+    }
+    return slot;
+}
+
 }  // namespace
 
 #ifndef FFM_GROUP_PROBE_VALU
@@ -189,7 +262,13 @@ __device__ __forceinline__ int cs_xp1(uint32_t v) { return (int)(v >> 25); }
 #endif
 
 #ifndef FFM_GROUP_WAVES
-#define FFM_GROUP_WAVES 6   // minimum waves per SIMD asked of the register allocator (G = 4 needs 71 VGPRs; the grid holds 6 per SIMD)
+#define FFM_GROUP_WAVES 6   // minimum waves per SIMD asked of the register allocator (G = 4 needs 73 VGPRs; the grid holds 6 per SIMD)
+#endif
+
+// The Neumann kernels' exact decide as a wave-cooperative pass (group_exact_coop); 0 builds the
+// per-lane serial pass (A/B builds, profiles/decide_stencil/).
+#ifndef FFM_GROUP_COOP_EXACT
+#define FFM_GROUP_COOP_EXACT 1
 #endif
 
 #ifndef FFM_GROUP_G
@@ -455,7 +534,12 @@ void core_group_kernel(CoreStepArgs a) {
                 bool to_exit = false;
                 uint32_t slot = lane_decide<NB, true, KD1>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32, pb.x, to_exit);
                 slot = live ? slot : kNoReq;
-                if (slot == kPending)   // u near a cdf boundary: the exact NumPy arithmetic decides
+                // u near a cdf boundary: the exact NumPy arithmetic decides
+                if (NB == 4 && FFM_GROUP_COOP_EXACT) {
+                    const unsigned long long pm = __ballot(slot == kPending);
+                    if (pm)   // wave-uniform, rare
+                        slot = group_exact_coop<W, PHW, TS>(pm, slot, v, pb.x, pb.y, grid, psff, tile, a.kD32, lane);
+                } else if (slot == kPending)
                     slot = NB == 4 ? lane_decide_exact<NB, true>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32,
                                                                  u53(pb.x, pb.y))
                                    : lane_decide_exact_arr<NB, true>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32,

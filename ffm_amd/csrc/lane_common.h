@@ -164,7 +164,8 @@ __device__ __forceinline__ uint32_t lane_decide(int pp, int PW, const uint16_t* 
 // Streams over the candidates, re-reading the scores from LDS in each of its passes
 // (max, sum, cdf total, search) with one candidate live at a time: this path sets
 // the kernel's register peak otherwise.  Neumann only (the 8-lane pairwise sum of
-// add.reduce needs every term at once: lane_decide_exact_arr).
+// add.reduce needs every term at once: lane_decide_exact_arr).  The group kernel's
+// Neumann builds run the same arithmetic across a wave instead (group_exact_coop).
 template <int NB, bool PRE = false, int DWS = -2>
 __device__ __forceinline__ float lane_score1(int k, int pp, int PW, const uint16_t* gk, const float* psff,
                                              const float* dk, int dd0, float kS, float kD, bool& valid) {
