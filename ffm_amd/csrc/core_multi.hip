@@ -215,8 +215,11 @@ void core_multi_kernel(CoreStepArgs a, int nsteps) {
                 CoreStepArgs ak = a;
                 ak.t = t;
                 wave_sync();
+                // without the candidate pass: in this kernel's step loop it costs two of the four
+                // instantiations a VGPR
                 for (int s = 0; s < 2; s++)
-                    if ((rsm >> (32 * s)) & 1ull) wave_reset_env(ak, ebase + (uint32_t)(e0 + s), keys, pfree, posb + s * 32, lane);
+                    if ((rsm >> (32 * s)) & 1ull)
+                        wave_reset_env<0, false, false>(ak, ebase + (uint32_t)(e0 + s), keys, pfree, posb + s * 32, lane);
             }
             // episode log (episode_log.h), keyed by the inner step's index; with auto_reset
             // every ended env is in rsm

@@ -68,6 +68,8 @@ struct ffm_engine {
     unsigned char* d_stage = nullptr;   // group kernel: the stage image (kernels.h), engine constants
     size_t stage_bytes = 0;
     int stage_q4 = 0;
+    int reset_m = 0;             // placement candidates aimed at (0: every key is ranked) and their key
+    uint32_t reset_thr = 0;      // threshold (CoreStepArgs::reset_thr); fixed at create
     uint16_t* d_pos = nullptr;
     int32_t* d_cnt = nullptr;
     float* d_dff = nullptr;
@@ -214,6 +216,17 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
     e->d.sff = nullptr;
     e->HW = HW;
     e->F = (int)fl.size();
+    // Placement candidates (wave_reset.h): about M = N + max(8, (N + 1) / 2) of the F keys fall
+    // below thr = floor(M * 2^32 / F), 48 for 32 agents.  FFM_RESET_CANDIDATES=<M> overrides M
+    // (A/B switch, read at create; 0: rank every key).  The division is done here, once: in the
+    // kernel it would be a loop invariant that every wave sets up.
+    {
+        const int N = d.n_agents, F = e->F;
+        int M = std::min(F, N + std::max(8, (N + 1) / 2));
+        if (const char* ov = std::getenv("FFM_RESET_CANDIDATES")) M = std::max(0, std::min(F, std::atoi(ov)));
+        e->reset_m = M;
+        e->reset_thr = M == 0 ? 0u : M == F ? 0xFFFFFFFFu : (uint32_t)(((uint64_t)M << 32) / (uint64_t)F);
+    }
     e->f64 = d.sff_dtype == FFM_SFF_F64;
     e->mt = d.rng_mode == FFM_RNG_MT;
     // NumPy weak-scalar promotion (NEP 50): python numbers become float32 next
@@ -509,6 +522,7 @@ static ffm::CoreStepArgs make_args(ffm_engine* e) {
     a.free_list = e->d_free;
     a.free_padded = e->d_free_padded;
     a.F = e->F;
+    a.reset_thr = e->reset_thr;
     a.stage = e->d_stage;
     a.stage_q4 = e->stage_q4;
     a.mt_np = e->d_mt_np;
@@ -972,6 +986,14 @@ int ffm_debug_stage_image(ffm_engine* e, void* out, int64_t cap, int64_t* n) {
     if (!out || e->stage_bytes == 0) return FFM_OK;
     if (cap < (int64_t)e->stage_bytes) return fail(FFM_E_INVALID, "stage_image: buffer too small (*n holds the size)");
     HIP_TRY(hipMemcpy(out, e->d_stage, e->stage_bytes, hipMemcpyDeviceToHost));
+    return FFM_OK;
+}
+
+// Diagnostic: the placement's candidate count M and key threshold in effect (fixed at create).
+int ffm_debug_reset_candidates(ffm_engine* e, int32_t* m, uint32_t* thr) {
+    if (!e || !m || !thr) return fail(FFM_E_INVALID, "bad args");
+    *m = e->reset_m;
+    *thr = e->reset_thr;
     return FFM_OK;
 }
 

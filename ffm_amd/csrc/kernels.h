@@ -43,6 +43,10 @@ struct CoreStepArgs {
     size_t scratch_stride;
     int no_step_count;        // group kernel: this launch leaves the `steps` counter alone (an env shard
                               // other than the step's first: engine.cpp, step shards)
+    uint32_t reset_thr;       // placement with F <= 128 (wave_reset.h): keys below it are the candidates that
+                              // get ranked; floor(M * 2^32 / F), set at create; 0: every key is ranked.
+                              // (Kept away from F: next to it the two load as a pair at kernel entry and
+                              // the threshold then holds a scalar register across the whole step loop.)
     // Group kernel: the engine-constant stage image (core_group_stage_build; 16-B aligned).  Its
     // first stage_q4 float4s are the block-shared LDS region byte for byte; the per-lane geometry
     // tables of both group sizes follow.  Built once at create: nothing in it has a setter.

@@ -15,7 +15,8 @@ __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, i
 // Philox placement of one env, stored straight to its global positions gpos[0..N)
 // (unpadded cell indices): all 64 lanes.
 // fl = padded free-cell list (LDS).  F <= 128: the (key, j) pairs go to LDS and
-// each lane ranks its two by broadcast reads -- few registers, because this
+// each lane ranks its two by broadcast reads (or, CAND, the one candidate pair the
+// lane is handed: DESIGN.md 4, the placement tail) -- few registers, because this
 // rarely-taken branch sits inside the step loop and would otherwise set the
 // kernel's VGPR peak.  Larger F: threshold the keys into an LDS candidate list
 // first (about 2N + 16 survive).
@@ -23,7 +24,8 @@ __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, i
 // caller's maps have at most 128 free cells, so the threshold path below is not built -- its
 // divisions by F and PW are loop invariants the compiler otherwise sets up in every wave of a
 // kernel that holds this call in a loop, whether or not an env is re-placed.
-template <int PWK = 0, bool SMALL = false>
+// CAND: the small-list path first tries the candidate pass below (a.reset_thr, set at create).
+template <int PWK = 0, bool SMALL = false, bool CAND = true>
 __device__ inline void wave_reset_env(const CoreStepArgs& a, uint32_t genv, unsigned long long* keys, const uint16_t* fl,
                                uint16_t* gpos, int lane) {
     const int PW = PWK > 0 ? PWK : a.W + 2;
@@ -38,6 +40,38 @@ __device__ inline void wave_reset_env(const CoreStepArgs& a, uint32_t genv, unsi
         const unsigned long long k1 =
             j1 < F ? ((unsigned long long)reset_key(a.key0, a.key1, a.t, genv, (uint32_t)j1) << 32) | (unsigned)j1
                    : ~0ull;
+        if (CAND) {
+            // Only the N smallest pairs are placed.  The pairs whose key is below reset_thr (about
+            // M = N + max(8, (N + 1) / 2) of the F) are the candidates: every other key is >=
+            // reset_thr and so above each of them, hence with C >= N candidates the N smallest
+            // pairs are all candidates and their rank among the candidates is their rank among
+            // all.  The C <= 64 of them are packed into keys[] (the j0 set, then the j1 set) and
+            // lane i ranks the one word keys[i] over (C + 1) / 2 reads.  C outside [N, 64] (about
+            // one placement in 1,150 at F = 100, N = 32), or reset_thr = 0: the full ranking below.
+            // A pad lane's ~0 key is never below reset_thr.
+            const bool c0 = (uint32_t)(k0 >> 32) < a.reset_thr, c1 = (uint32_t)(k1 >> 32) < a.reset_thr;
+            const unsigned long long m0 = __ballot(c0), m1 = __ballot(c1);
+            const int C0 = __popcll(m0), C = C0 + __popcll(m1);
+            if (C >= N && C <= 64) {
+                // keys[C] <= keys[64] lies inside the list the full ranking writes: C <= F, and
+                // an odd C equal to F is that path's own pad slot
+                if (c0) keys[lanes_below(m0)] = k0;
+                if (c1) keys[C0 + lanes_below(m1)] = k1;
+                if (lane == 0 && (C & 1)) keys[C] = ~0ull;
+                wave_sync();
+                const unsigned long long ki = lane < C ? keys[lane] : ~0ull;
+                int r = 0;
+                const ulonglong2* kv = reinterpret_cast<const ulonglong2*>(keys);
+#pragma unroll 4
+                for (int q = 0; q < (C + 1) / 2; q++) {
+                    const ulonglong2 p = kv[q];
+                    r += (p.x < ki ? 1 : 0) + (p.y < ki ? 1 : 0);
+                }
+                if (lane < C && r < N) gpos[r] = (uint16_t)unpad(fl[(int)(ki & 0xFFu)], PW);
+                wave_sync();
+                return;
+            }
+        }
         if (j0 < F) keys[j0] = k0;
         if (j1 < F) keys[j1] = k1;
         if (lane == 0 && (F & 1)) keys[F] = ~0ull;   // pad to pairs: ~0 is never below a key

@@ -30,7 +30,7 @@ EXPORTED = [
     "ffm_engine_set_step_index", "ffm_engine_set_fused_steps", "ffm_np_expf_device",
     "ffm_engine_set_trajectory_capture", "ffm_engine_drain_trajectory",
     "ffm_engine_set_episode_log", "ffm_engine_drain_episodes", "ffm_engine_get_episode_stats",
-    "ffm_debug_stage_image",
+    "ffm_debug_stage_image", "ffm_debug_reset_candidates",
     "ffm_learner_create", "ffm_learner_destroy", "ffm_learner_reset", "ffm_learner_reset_envs", "ffm_learner_step",
     "ffm_learner_set_state", "ffm_learner_get_state", "ffm_learner_get_episodes",
     "ffm_learner_set_mt_state", "ffm_learner_get_mt_state", "ffm_learner_get_counters",
@@ -139,6 +139,7 @@ def load_library():
     L.ffm_engine_get_episode_stats.argtypes = [P, P, i32, P, i32, P]
     L.ffm_np_expf_device.argtypes = [P, P, i64, P]
     L.ffm_debug_stage_image.argtypes = [P, P, i64, C.POINTER(i64)]
+    L.ffm_debug_reset_candidates.argtypes = [P, C.POINTER(i32), C.POINTER(C.c_uint32)]
     L.ffm_debug_launch_info.argtypes = [P, P, C.c_int]   # diagnostic, not in the ABI header
     L.ffm_debug_launch_info.restype = C.c_int
     L.ffm_learner_create.argtypes = [C.POINTER(EngineDesc), C.POINTER(LearnDesc), C.POINTER(P)]
@@ -582,6 +583,13 @@ class Engine:
         if n.value:
             _check(self._L.ffm_debug_stage_image(self._h, _ptr(out), n.value, C.byref(n)))
         return out
+
+    def reset_candidates(self) -> dict:
+        """The placement's candidate count M and key threshold in effect (diagnostic,
+        ffm_debug_reset_candidates; FFM_RESET_CANDIDATES at create overrides M)."""
+        m, thr = C.c_int32(), C.c_uint32()
+        _check(self._L.ffm_debug_reset_candidates(self._h, C.byref(m), C.byref(thr)))
+        return {"M": int(m.value), "thr": int(thr.value)}
 
     @property
     def step_index(self) -> int:

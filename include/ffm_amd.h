@@ -520,6 +520,11 @@ int ffm_np_expf_device(const float* x, float* y, int64_t n, void* stream);
  * the size in bytes (0: the engine steps with another kernel); the copy is made when out is
  * not NULL and cap >= *n. */
 int ffm_debug_stage_image(ffm_engine* eng, void* out, int64_t cap, int64_t* n);
+/* The placement's candidate pass (free lists of <= 128 cells): only keys below *thr =
+ * floor(*m * 2^32 / F) are ranked, *m = min(F, N + max(8, (N + 1) / 2)) unless the environment
+ * variable FFM_RESET_CANDIDATES set another count when the engine was created (0: every key is
+ * ranked, *thr = 0; *m = F: *thr = 2^32 - 1).  The placements are the same for every *m. */
+int ffm_debug_reset_candidates(ffm_engine* eng, int32_t* m, uint32_t* thr);
 
 #ifdef __cplusplus
 }
