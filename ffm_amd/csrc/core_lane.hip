@@ -98,11 +98,17 @@ __host__ __device__ inline size_t lane_shared_bytes(int PHW, int F) {
 #ifndef FFM_LANE_WAVES
 #define FFM_LANE_WAVES 7   // diagnostic builds may lower / raise the 12x12 Neumann occupancy ask
 #endif
-template <int NB, int HT>
-constexpr int lane_waves() { return (NB == 4 && HT == 12) ? FFM_LANE_WAVES : 1; }
+#ifndef FFM_LANE_PEP_WAVES
+#define FFM_LANE_PEP_WAVES 7   // the same ask of the 12x12 Neumann build with per-env parameters
+#endif
+template <int NB, int HT, bool PEP = false>
+constexpr int lane_waves() { return (NB == 4 && HT == 12) ? (PEP ? FFM_LANE_PEP_WAVES : FFM_LANE_WAVES) : 1; }
 
-template <int NB, int HT, int WT, bool EPL>   // EPL: with the episode log (episode_log.h)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lane_waves<NB, HT>(), 8)))
+// EPL: with the episode log (episode_log.h).  PEP: with per-env parameters (a.envp, kernels.h):
+// the lane's env's record is prefetched with the pair's state; decide takes its kS32 / kD32, the
+// stencil the c0 / c1 of each float4 slot's env, the count store and the placement its N.
+template <int NB, int HT, int WT, bool EPL, bool PEP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lane_waves<NB, HT, PEP>(), 8)))
 void core_lane_kernel(CoreStepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int H = HT ? HT : a.H, W = WT ? WT : a.W;
@@ -159,6 +165,8 @@ void core_lane_kernel(CoreStepArgs a) {
     struct LaneState {
         float4 d0, d1;
         int pos, cnt;
+        float4 pr;   // PEP: kS32, kD32, c0, c1 of the lane's env
+        int N;       // PEP: its N
     };
     auto load = [&](int gg, LaneState& st) {
         const int e0 = (gg < 0 ? 0 : gg) * 2;
@@ -169,6 +177,11 @@ void core_lane_kernel(CoreStepArgs a) {
         const __amdgpu_buffer_rsrc_t rd = pair_rsrc(a.dff + (long long)e0 * HW, nenv * HW * 4);
         st.d0 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rd, off_d0, 0, 0));
         st.d1 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rd, off_d0 + 1024, 0, 0));
+        if constexpr (PEP) {   // one record per half-wave (broadcast); a pair past the end reads zeros
+            const __amdgpu_buffer_rsrc_t rp = pair_rsrc(a.envp + e0, nenv * (int)sizeof(EnvParams));
+            st.pr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rp, sub * (int)sizeof(EnvParams), 0, 0));
+            st.N = (int)__builtin_amdgcn_raw_buffer_load_b32(rp, sub * (int)sizeof(EnvParams) + 24, 0, 0);
+        }
     };
     LaneState cur;
     load(g < ngroups ? g : -1, cur);
@@ -212,6 +225,7 @@ void core_lane_kernel(CoreStepArgs a) {
         const int nenv = min(E32 - e0, 2);
         const bool env_ok = sub < nenv;
         const uint32_t genv = ebase + (uint32_t)(e0 + sub);
+        const float kS32 = PEP ? cur.pr.x : a.kS32, kD32 = PEP ? cur.pr.y : a.kD32;
 
         // ---- agent cell and occupancy mark ----------------------------------------------
         const bool live = env_ok && al < cnt;
@@ -240,11 +254,11 @@ void core_lane_kernel(CoreStepArgs a) {
         words[lane] = make_uint2(pb.z, pb.w);   // the friction draw, if this agent owns a contested target
         bool to_exit = false;
         uint32_t slot = (FFM_LANE_ABLATE & 16) ? (uint32_t)NB
-                                               : lane_decide<NB>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32, pb.x, to_exit);
+                                               : lane_decide<NB>(pp, PW, gk, psff, dk, dd0, kS32, kD32, pb.x, to_exit);
         slot = live ? slot : kNoReq;
         if (slot == kPending)   // u near a cdf boundary: the exact NumPy arithmetic decides
-            slot = NB == 4 ? lane_decide_exact<NB>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32, u53(pb.x, pb.y))
-                           : lane_decide_exact_arr<NB>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32, u53(pb.x, pb.y));
+            slot = NB == 4 ? lane_decide_exact<NB>(pp, PW, gk, psff, dk, dd0, kS32, kD32, u53(pb.x, pb.y))
+                           : lane_decide_exact_arr<NB>(pp, PW, gk, psff, dk, dd0, kS32, kD32, u53(pb.x, pb.y));
         // the request goes into the agent's own grid cell: direction code in the high byte
         if (live)
             *mine = (uint16_t)(DirCodes::kAgent | (uint32_t)al |
@@ -307,7 +321,7 @@ void core_lane_kernel(CoreStepArgs a) {
         // prefetched state are never live together.
         __builtin_amdgcn_raw_buffer_store_b16((uint16_t)unpad(np, PW), pair_rsrc(a.pos + (long long)e0 * A, nenv * A * 2),
                                               keep ? (sub * A + newidx) * 2 : kOOB, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b32((unsigned)(rs ? a.N : newcnt), pair_rsrc(a.cnt + e0, nenv * 4),
+        __builtin_amdgcn_raw_buffer_store_b32((unsigned)(rs ? (PEP ? cur.N : a.N) : newcnt), pair_rsrc(a.cnt + e0, nenv * 4),
                                               al == 0 ? off_cnt : kOOB, 0, 0);
         if (rsm) {   // wave-uniform, rare
             if (a.episodes && al == 0 && rs) a.episodes[e0 + sub] += 1;
@@ -317,6 +331,18 @@ void core_lane_kernel(CoreStepArgs a) {
         // episode log (episode_log.h): with auto_reset every ended env is in rsm
         if (EPL && (rsm || !a.auto_reset))
             eplog_end_wave(a, env_ok && al == 0 && newcnt == 0 && cnt > 0, rs && al == 0, e0 + sub, a.t, lane);
+
+        // PEP: c0, c1 of each float4 slot's env (zs0 / zs1, not the lane's sub), from the records
+        // lanes 0 and 32 hold
+        float c0s0 = a.c0, c1s0 = a.c1, c0s1 = a.c0, c1s1 = a.c1;
+        if constexpr (PEP) {
+            auto rl = [](float v, int l) {
+                return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+            };
+            const float c0a = rl(cur.pr.z, 0), c0b = rl(cur.pr.z, 32), c1a = rl(cur.pr.w, 0), c1b = rl(cur.pr.w, 32);
+            c0s0 = zs0 == 0 ? c0a : c0b; c1s0 = zs0 == 0 ? c1a : c1b;
+            c0s1 = zs1 == 0 ? c0a : c0b; c1s1 = zs1 == 0 ? c1a : c1b;
+        }
 
         LSTAMP(4);
         // ---- next group's HBM loads, in flight across the stencil, the stores and the
@@ -331,17 +357,17 @@ void core_lane_kernel(CoreStepArgs a) {
 
         LSTAMP(5);
         // ---- update_dff (model/ffm_core.py:106-117): B = c0 * D, A = B + sum c1 * B[nb] -----
-        auto stencil = [&](int tb, bool yl, bool yr, float4& out) {
+        auto stencil = [&](int tb, bool yl, bool yr, float c0, float c1, float4& out) {
             const float* p = tile + tb;
             float b[3][6];   // rows dx = -1..1, columns -1..4 (B values)
 #pragma unroll
             for (int dx = -1; dx <= 1; dx++) {
                 const float4 u = *reinterpret_cast<const float4*>(p + dx * W);
-                b[dx + 1][1] = a.c0 * u.x; b[dx + 1][2] = a.c0 * u.y;
-                b[dx + 1][3] = a.c0 * u.z; b[dx + 1][4] = a.c0 * u.w;
+                b[dx + 1][1] = c0 * u.x; b[dx + 1][2] = c0 * u.y;
+                b[dx + 1][3] = c0 * u.z; b[dx + 1][4] = c0 * u.w;
                 if (NB == 4 && dx != 0) continue;
-                b[dx + 1][0] = a.c0 * tile[yl ? 0 : tb + dx * W - 1];   // tile[0] == 0
-                b[dx + 1][5] = a.c0 * tile[yr ? 0 : tb + dx * W + 4];
+                b[dx + 1][0] = c0 * tile[yl ? 0 : tb + dx * W - 1];   // tile[0] == 0
+                b[dx + 1][5] = c0 * tile[yr ? 0 : tb + dx * W + 4];
             }
             float o[4];
 #pragma unroll
@@ -349,7 +375,7 @@ void core_lane_kernel(CoreStepArgs a) {
                 float acc = b[1][j + 1];
 #pragma unroll
                 for (int s = 0; s < NB; s++) {
-                    const float t = a.c1 * b[1 + nb_dx<NB>(s)][j + 1 + nb_dy<NB>(s)];   // :113
+                    const float t = c1 * b[1 + nb_dx<NB>(s)][j + 1 + nb_dy<NB>(s)];   // :113
                     acc = acc + t;
                 }
                 o[j] = acc < 1e-4f ? 0.0f : acc;                                       // :116-117
@@ -357,8 +383,8 @@ void core_lane_kernel(CoreStepArgs a) {
             out = make_float4(o[0], o[1], o[2], o[3]);
         };
         float4 o0 = make_float4(0.f, 0.f, 0.f, 0.f), o1 = o0;
-        if (tb0 >= 0) stencil(tb0, yl0, yr0, o0);
-        if (!(FFM_LANE_ABLATE & 2) && tb1 >= 0) stencil(tb1, yl1, yr1, o1);
+        if (tb0 >= 0) stencil(tb0, yl0, yr0, PEP ? c0s0 : a.c0, PEP ? c1s0 : a.c1, o0);
+        if (!(FFM_LANE_ABLATE & 2) && tb1 >= 0) stencil(tb1, yl1, yr1, PEP ? c0s1 : a.c0, PEP ? c1s1 : a.c1, o1);
 
         LSTAMP(6);
         // ---- DFF stores (an env reset this step starts its next episode with a zero DFF) --
@@ -384,7 +410,11 @@ void core_lane_kernel(CoreStepArgs a) {
             const int bit = w * 32 + __builtin_ctz(m);
             m &= m - 1u;
             const int e = (g_first + (bit >> 1) * wstride) * 2 + (bit & 1);
-            if (!(FFM_LANE_ABLATE & 64)) wave_reset_env(a, ebase + (uint32_t)e, keys, pfree, a.pos + (long long)e * A, lane);
+            if (FFM_LANE_ABLATE & 64) continue;
+            if constexpr (PEP)   // the env's own N and threshold, read here: rare, nothing of the step is live
+                wave_reset_env(a, ebase + (uint32_t)e, keys, pfree, a.pos + (long long)e * A, lane, a.envp[e].N,
+                               a.envp[e].reset_thr);
+            else wave_reset_env(a, ebase + (uint32_t)e, keys, pfree, a.pos + (long long)e * A, lane);
         }
     }
 
@@ -415,12 +445,19 @@ static hipError_t lane_op(const CoreStepArgs& a, int blocks, hipStream_t s, int 
         return hipErrorInvalidConfiguration;   // the grid must give every wave <= kLaneMaxPairs pairs
     if (op) {
         *occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_lane_kernel<NB, HT, WT, false>, 256, smem) != hipSuccess)
-            *occ = 0;
+        const hipError_t he = a.envp ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                                           occ, core_lane_kernel<NB, HT, WT, false, true>, 256, smem)
+                                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                                           occ, core_lane_kernel<NB, HT, WT, false, false>, 256, smem);
+        if (he != hipSuccess) *occ = 0;
         return hipSuccess;
     }
-    if (a.ep_start) core_lane_kernel<NB, HT, WT, true><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
-    else core_lane_kernel<NB, HT, WT, false><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
+    const dim3 gd((unsigned)blocks), bd(256);
+    if (a.envp) {   // per-env parameters
+        if (a.ep_start) core_lane_kernel<NB, HT, WT, true, true><<<gd, bd, smem, s>>>(a);
+        else core_lane_kernel<NB, HT, WT, false, true><<<gd, bd, smem, s>>>(a);
+    } else if (a.ep_start) core_lane_kernel<NB, HT, WT, true, false><<<gd, bd, smem, s>>>(a);
+    else core_lane_kernel<NB, HT, WT, false, false><<<gd, bd, smem, s>>>(a);
     return hipGetLastError();
 }
 

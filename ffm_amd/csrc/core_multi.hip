@@ -57,7 +57,9 @@ __host__ __device__ inline size_t multi_shared_bytes(int PHW, int F) {
 #define FFM_MULTI_WAVES 1   // minimum waves per SIMD asked of the register allocator
 #endif
 
-template <int NB, int HT, int WT, bool EPL>   // EPL: with the episode log (episode_log.h)
+// EPL: with the episode log (episode_log.h).  PEP: with per-env parameters (a.envp), as the lane
+// kernel's: the record is loaded once per launch with the pair, nothing is re-read in the k steps.
+template <int NB, int HT, int WT, bool EPL, bool PEP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FFM_MULTI_WAVES, 8)))
 void core_multi_kernel(CoreStepArgs a, int nsteps) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -131,6 +133,21 @@ void core_multi_kernel(CoreStepArgs a, int nsteps) {
         float4 o1 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rd, 16 * lane + 1024, 0, 0));
         if (tb0 >= 0) *reinterpret_cast<float4*>(tile + tb0) = o0;
         if (tb1 >= 0) *reinterpret_cast<float4*>(tile + tb1) = o1;
+        // the lane's env's kS32, kD32 and N; c0, c1 of each float4 slot's env (zs0 / zs1)
+        float kS32 = a.kS32, kD32 = a.kD32, c0s0 = a.c0, c1s0 = a.c1, c0s1 = a.c0, c1s1 = a.c1;
+        int Nenv = a.N;
+        if constexpr (PEP) {   // one record per half-wave (broadcast); an env past the end reads zeros
+            const __amdgpu_buffer_rsrc_t rq = pair_rsrc(a.envp + e0, nenv * (int)sizeof(EnvParams));
+            const float4 pr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rq, sub * (int)sizeof(EnvParams), 0, 0));
+            Nenv = (int)__builtin_amdgcn_raw_buffer_load_b32(rq, sub * (int)sizeof(EnvParams) + 24, 0, 0);
+            auto rl = [](float v, int l) {
+                return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+            };
+            const float c0a = rl(pr.z, 0), c0b = rl(pr.z, 32), c1a = rl(pr.w, 0), c1b = rl(pr.w, 32);
+            kS32 = pr.x; kD32 = pr.y;
+            c0s0 = zs0 == 0 ? c0a : c0b; c1s0 = zs0 == 0 ? c1a : c1b;
+            c0s1 = zs1 == 0 ? c0a : c0b; c1s1 = zs1 == 0 ? c1a : c1b;
+        }
         wave_sync();
 
         for (int k = 0; k < nsteps; k++) {
@@ -154,11 +171,11 @@ void core_multi_kernel(CoreStepArgs a, int nsteps) {
             const uint4 pb = philox(make_uint4(t, genv, (uint32_t)al, kPurDecide << 28), a.key0, a.key1);
             words[lane] = make_uint2(pb.z, pb.w);
             bool to_exit = false;
-            uint32_t slot = lane_decide<NB>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32, pb.x, to_exit);
+            uint32_t slot = lane_decide<NB>(pp, PW, gk, psff, dk, dd0, kS32, kD32, pb.x, to_exit);
             slot = live ? slot : kNoReq;
             if (slot == kPending)
-                slot = NB == 4 ? lane_decide_exact<NB>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32, u53(pb.x, pb.y))
-                               : lane_decide_exact_arr<NB>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32, u53(pb.x, pb.y));
+                slot = NB == 4 ? lane_decide_exact<NB>(pp, PW, gk, psff, dk, dd0, kS32, kD32, u53(pb.x, pb.y))
+                               : lane_decide_exact_arr<NB>(pp, PW, gk, psff, dk, dd0, kS32, kD32, u53(pb.x, pb.y));
             if (live)
                 *mine = (uint16_t)(DirCodes::kAgent | (uint32_t)al |
                                    ((slot <= (uint32_t)NB ? slot : DirCodes::kNoDir) << 8));
@@ -218,29 +235,34 @@ void core_multi_kernel(CoreStepArgs a, int nsteps) {
                 // without the candidate pass: in this kernel's step loop it costs two of the four
                 // instantiations a VGPR
                 for (int s = 0; s < 2; s++)
-                    if ((rsm >> (32 * s)) & 1ull)
-                        wave_reset_env<0, false, false>(ak, ebase + (uint32_t)(e0 + s), keys, pfree, posb + s * 32, lane);
+                    if ((rsm >> (32 * s)) & 1ull) {
+                        if constexpr (PEP)
+                            wave_reset_env<0, false, false>(ak, ebase + (uint32_t)(e0 + s), keys, pfree, posb + s * 32, lane,
+                                                            __builtin_amdgcn_readlane(Nenv, 32 * s), 0u);
+                        else
+                            wave_reset_env<0, false, false>(ak, ebase + (uint32_t)(e0 + s), keys, pfree, posb + s * 32, lane);
+                    }
             }
             // episode log (episode_log.h), keyed by the inner step's index; with auto_reset
             // every ended env is in rsm
             if (EPL && (rsm || !a.auto_reset))
                 eplog_end_wave(a, env_ok && al == 0 && newcnt == 0 && cnt > 0, rs && al == 0, e0 + sub, t, lane);
-            cnt = rs ? a.N : newcnt;
+            cnt = rs ? Nenv : newcnt;
             wave_sync();
             cpos = posb[lane];
 
             // ---- update_dff (model/ffm_core.py:106-117) back into the tile ------------------
-            auto stencil = [&](int tb, bool yl, bool yr, float4& out) {
+            auto stencil = [&](int tb, bool yl, bool yr, float c0, float c1, float4& out) {
                 const float* p = tile + tb;
                 float b[3][6];
 #pragma unroll
                 for (int dx = -1; dx <= 1; dx++) {
                     const float4 u = *reinterpret_cast<const float4*>(p + dx * W);
-                    b[dx + 1][1] = a.c0 * u.x; b[dx + 1][2] = a.c0 * u.y;
-                    b[dx + 1][3] = a.c0 * u.z; b[dx + 1][4] = a.c0 * u.w;
+                    b[dx + 1][1] = c0 * u.x; b[dx + 1][2] = c0 * u.y;
+                    b[dx + 1][3] = c0 * u.z; b[dx + 1][4] = c0 * u.w;
                     if (NB == 4 && dx != 0) continue;
-                    b[dx + 1][0] = a.c0 * tile[yl ? 0 : tb + dx * W - 1];
-                    b[dx + 1][5] = a.c0 * tile[yr ? 0 : tb + dx * W + 4];
+                    b[dx + 1][0] = c0 * tile[yl ? 0 : tb + dx * W - 1];
+                    b[dx + 1][5] = c0 * tile[yr ? 0 : tb + dx * W + 4];
                 }
                 float ov[4];
 #pragma unroll
@@ -248,7 +270,7 @@ void core_multi_kernel(CoreStepArgs a, int nsteps) {
                     float acc = b[1][j + 1];
 #pragma unroll
                     for (int s = 0; s < NB; s++) {
-                        const float tt = a.c1 * b[1 + nb_dx<NB>(s)][j + 1 + nb_dy<NB>(s)];
+                        const float tt = c1 * b[1 + nb_dx<NB>(s)][j + 1 + nb_dy<NB>(s)];
                         acc = acc + tt;
                     }
                     ov[j] = acc < 1e-4f ? 0.0f : acc;
@@ -257,8 +279,8 @@ void core_multi_kernel(CoreStepArgs a, int nsteps) {
             };
             o0 = make_float4(0.f, 0.f, 0.f, 0.f);
             o1 = o0;
-            if (tb0 >= 0) stencil(tb0, yl0, yr0, o0);
-            if (tb1 >= 0) stencil(tb1, yl1, yr1, o1);
+            if (tb0 >= 0) stencil(tb0, yl0, yr0, PEP ? c0s0 : a.c0, PEP ? c1s0 : a.c1, o0);
+            if (tb1 >= 0) stencil(tb1, yl1, yr1, PEP ? c0s1 : a.c0, PEP ? c1s1 : a.c1, o1);
             {
                 const bool r0 = (rsm & 1ull) != 0, r1 = (rsm >> 32) != 0;
                 const bool z0 = zs0 == 0 ? r0 : (zs0 == 1 && r1), z1 = zs1 == 0 ? r0 : (zs1 == 1 && r1);
@@ -297,14 +319,18 @@ static hipError_t multi_op(const CoreStepArgs& a, int nsteps, int blocks, hipStr
     const size_t smem = core_multi_smem_bytes(a.H, a.W, a.F, 4);
     if (op) {
         *occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_multi_kernel<NB, HT, WT, false>, 256, smem) != hipSuccess)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_multi_kernel<NB, HT, WT, false, false>, 256, smem) != hipSuccess)
             *occ = 0;
         return hipSuccess;
     }
     if (a.A > 32 || a.N > 32 || a.W % 4 != 0 || a.H * a.W > 256 || nsteps < 1)
         return hipErrorInvalidConfiguration;   // shapes the kernel assumes
-    if (a.ep_start) core_multi_kernel<NB, HT, WT, true><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a, nsteps);
-    else core_multi_kernel<NB, HT, WT, false><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a, nsteps);
+    const dim3 gd((unsigned)blocks), bd(256);
+    if (a.envp) {   // per-env parameters
+        if (a.ep_start) core_multi_kernel<NB, HT, WT, true, true><<<gd, bd, smem, s>>>(a, nsteps);
+        else core_multi_kernel<NB, HT, WT, false, true><<<gd, bd, smem, s>>>(a, nsteps);
+    } else if (a.ep_start) core_multi_kernel<NB, HT, WT, true, false><<<gd, bd, smem, s>>>(a, nsteps);
+    else core_multi_kernel<NB, HT, WT, false, false><<<gd, bd, smem, s>>>(a, nsteps);
     return hipGetLastError();
 }
 

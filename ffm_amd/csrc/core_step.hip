@@ -650,11 +650,13 @@ __device__ __forceinline__ int block_excl_scan(bool flag, int* swsum, int& total
 // Philox placement of env e by the whole workgroup: the N free cells
 // with the smallest (key_j, j).  Candidates under a threshold (~2N + 16 of them) are
 // kept in `keys` (KC of them) and ranked; more than KC take an exact recomputing path.
-template <int BS>
+// PEP: the env's own N (per-env parameters, a.envp).
+template <int BS, bool PEP = false>
 __device__ void block_place_env(const CoreStepArgs& a, long long e, unsigned long long* keys, int KC, int* swsum) {
     const int tid = threadIdx.x;
     const uint32_t genv = (uint32_t)(a.env_base + e);
-    uint32_t T = reset_threshold(a.N, a.F);
+    const int N = PEP ? a.envp[e].N : a.N;
+    uint32_t T = reset_threshold(N, a.F);
     int C = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
         C = 0;
@@ -671,7 +673,7 @@ __device__ void block_place_env(const CoreStepArgs& a, long long e, unsigned lon
             if (cand && C + ex < KC) keys[C + ex] = ((unsigned long long)key << 32) | (unsigned)j;
             C += tot;
         }
-        if ((C >= a.N && C <= KC) || T == 0xFFFFFFFFu) break;
+        if ((C >= N && C <= KC) || T == 0xFFFFFFFFu) break;
         if (C > KC) break;       // too many to keep: the recomputing path below
         T = 0xFFFFFFFFu;
     }
@@ -682,7 +684,7 @@ __device__ void block_place_env(const CoreStepArgs& a, long long e, unsigned lon
             int rank = 0;
 #pragma unroll 4
             for (int q = 0; q < C; q++) rank += keys[q] < ki ? 1 : 0;
-            if (rank < a.N) a.pos[e * a.A + rank] = a.free_list[(int)(ki & 0xFFFFFFFFu)];
+            if (rank < N) a.pos[e * a.A + rank] = a.free_list[(int)(ki & 0xFFFFFFFFu)];
         }
     } else {
         // Exact but slow (keys recomputed per comparison): the candidates exceed KC.
@@ -691,12 +693,12 @@ __device__ void block_place_env(const CoreStepArgs& a, long long e, unsigned lon
             if (kj > T) continue;
             const unsigned long long ki = ((unsigned long long)kj << 32) | (unsigned)j;
             int rank = 0;
-            for (int q = 0; q < a.F && rank < a.N; q++) {
+            for (int q = 0; q < a.F && rank < N; q++) {
                 const unsigned long long kq =
                     ((unsigned long long)reset_key(a.key0, a.key1, a.t, genv, (uint32_t)q) << 32) | (unsigned)q;
                 rank += kq < ki ? 1 : 0;
             }
-            if (rank < a.N) a.pos[e * a.A + rank] = a.free_list[j];
+            if (rank < N) a.pos[e * a.A + rank] = a.free_list[j];
         }
     }
     __syncthreads();
@@ -721,7 +723,11 @@ __device__ __forceinline__ CT req_cell(uint32_t slot, int pp, int PW) {
 // The Neumann float32 kernels fit 8 waves per SIMD (57 VGPRs, 78 SGPRs, no spills) and with
 // the placement keys sharing the dead arrays' LDS (block_carve) four 512-lane blocks fit a
 // CU: C3 137.3 -> 129.7 us.  Moore and float64 would spill under that bound: theirs stays 1.
-template <int NB, bool F64, bool MT, int BS, bool BIG, bool EPL>   // EPL: as core_wave_kernel's
+// EPL: as core_wave_kernel's.  PEP (Philox only): per-env parameters -- the block's K records
+// (a.envp, kernels.h) are staged into LDS behind the carve in the prologue; decide takes the
+// agent's env's kS32 / kD32 / kS64, the stencil the cell's env's c0 / c1, the count store and the
+// placement the env's N.
+template <int NB, bool F64, bool MT, int BS, bool BIG, bool EPL, bool PEP>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(NB == 4 && !F64 ? FFM_BLOCK_WAVES : 1, 8)))
 void core_block_kernel(CoreStepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -751,6 +757,7 @@ void core_block_kernel(CoreStepArgs a) {
     int* sseg = sreset + a.K;                              // [K] scan segment base
     int* swsum = sseg + a.K;                               // [BS/64]
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(gbase + cv.keys);
+    const EnvParams* const sp = reinterpret_cast<const EnvParams*>(smem + cv.lds);   // PEP: [K], past the carve
 
     const int nA = K * A;
     const int nP = K * PHW;
@@ -803,6 +810,11 @@ void core_block_kernel(CoreStepArgs a) {
         scnt[tid] = a.cnt[e0 + tid];
         sreset[tid] = 0;
     }
+    if constexpr (PEP) {   // the K envs' records, dword by dword
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(a.envp + e0);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(smem + cv.lds);
+        for (int i = tid; i < K * (int)(sizeof(EnvParams) / 4); i += BS) dst[i] = src[i];
+    }
     __syncthreads();
     for (AgentIdx ag = ag0; ag.it < nA; ag.advance()) {
         const int it = ag.it;
@@ -845,9 +857,11 @@ void core_block_kernel(CoreStepArgs a) {
                                  : philox(make_uint4(a.t, (uint32_t)(a.env_base + e0 + k), (uint32_t)i, kPurDecide << 28),
                                           a.key0, a.key1);
             reinterpret_cast<uint2*>(gbase + cv.u)[it] = make_uint2(pb.z, pb.w);
+            const float kS32 = PEP ? sp[k].kS32 : a.kS32, kD32 = PEP ? sp[k].kD32 : a.kD32;
             if (F64) {
                 r = req_cell<NB, CT>(decide<NB, F64, GT>(pp, PW, grid + k * PHW, psff32, psff64, tile + k * PHW, 0, 0,
-                                                         a.kS32, a.kD32, a.kS64, DrawFixed{u53(pb.x, pb.y)}), pp, PW);
+                                                         kS32, kD32, PEP ? sp[k].kS64 : a.kS64,
+                                                         DrawFixed{u53(pb.x, pb.y)}), pp, PW);
             } else {
                 // the trimmed fast pass of the small-env kernels (float32 u, masked scores, no
                 // double conversion; the tile has the grid's layout: DWS = 0), the exact NumPy
@@ -855,12 +869,12 @@ void core_block_kernel(CoreStepArgs a) {
                 bool to_exit = false;
                 uint32_t slot = (FFM_BLOCK_ABLATE & 8) ? (uint32_t)NB   // diagnostic: everyone stays
                                 : lane_decide<NB, false, false, 0>(pp, PW, grid + k * PHW, psff32, tile + k * PHW, 0,
-                                                                 a.kS32, a.kD32, pb.x, to_exit);
+                                                                 kS32, kD32, pb.x, to_exit);
                 if (slot == kPending)
                     slot = NB == 4 ? lane_decide_exact<NB, false, 0>(pp, PW, grid + k * PHW, psff32, tile + k * PHW, 0,
-                                                                     a.kS32, a.kD32, u53(pb.x, pb.y))
+                                                                     kS32, kD32, u53(pb.x, pb.y))
                                    : lane_decide_exact_arr<NB, false, 0>(pp, PW, grid + k * PHW, psff32, tile + k * PHW,
-                                                                         0, a.kS32, a.kD32, u53(pb.x, pb.y));
+                                                                         0, kS32, kD32, u53(pb.x, pb.y));
                 r = req_cell<NB, CT>(slot, pp, PW);
             }
         }
@@ -997,7 +1011,7 @@ void core_block_kernel(CoreStepArgs a) {
         __syncthreads();
         for (int k = 0; k < K; k++) {
             if (!sreset[k]) continue;   // block-uniform
-            block_place_env<BS>(a, e0 + k, keys, KC, swsum);
+            block_place_env<BS, PEP>(a, e0 + k, keys, KC, swsum);
         }
     }
 
@@ -1016,7 +1030,7 @@ void core_block_kernel(CoreStepArgs a) {
         if (blockIdx.x == 0) atomicAdd(&slot[3], 1ull);
     }
     if (tid < K) {
-        a.cnt[e0 + tid] = sreset[tid] ? a.N : snew[tid];
+        a.cnt[e0 + tid] = sreset[tid] ? (PEP ? sp[tid].N : a.N) : snew[tid];
         if (sreset[tid] && a.episodes) a.episodes[e0 + tid] += 1;
         if (EPL) {   // episode log (episode_log.h)
             if (snew[tid] == 0 && scnt[tid] > 0) eplog_end_one(a, e0 + tid, a.t);
@@ -1028,7 +1042,6 @@ void core_block_kernel(CoreStepArgs a) {
     // B = c0 * D (:109) is formed on the fly from each operand, rounded exactly as the
     // reference's separate pass, so the tile is read once and needs no extra barrier.
     __syncthreads();   // every deposit of the resolve is in the tile
-    const float c0 = a.c0, c1 = a.c1;
     if ((W & 3) == 0) {
         // four cells of a row per thread: 16-B DFF stores, shared row operands
         const int W4 = W >> 2;
@@ -1036,6 +1049,7 @@ void core_block_kernel(CoreStepArgs a) {
         for (int q = tid; q < K * H * W4; q += BS, ix.advance()) {
             const int k = ix.k, x = ix.r, y = 4 * ix.c;
             const float* p = tile + k * PHW + (x + 1) * PW + y + 1;
+            const float c0 = PEP ? sp[k].c0 : a.c0, c1 = PEP ? sp[k].c1 : a.c1;
             float b[3][6];   // rows dx = -1..1, columns y-1..y+4
 #pragma unroll
             for (int dx = -1; dx <= 1; dx++)
@@ -1064,6 +1078,7 @@ void core_block_kernel(CoreStepArgs a) {
         for (int c = tid; c < K * HW; c += BS, ix.advance()) {
             const int k = ix.k, x = ix.r, y = ix.c;
             const float* p = tile + k * PHW + (x + 1) * PW + y + 1;
+            const float c0 = PEP ? sp[k].c0 : a.c0, c1 = PEP ? sp[k].c1 : a.c1;
             float acc = c0 * *p;
 #pragma unroll
             for (int q = 0; q < NB; q++) {
@@ -1082,6 +1097,8 @@ void core_block_kernel(CoreStepArgs a) {
 // mask (device, [E] bytes; ffm_engine_reset_envs): only the envs with a nonzero byte are
 // re-placed, their DFF row zeroed and their position row cleared here (the whole-engine reset
 // clears every row by memset beforehand).
+// PEP: the env's own N and candidate threshold (per-env parameters, a.envp).
+template <bool PEP>
 __global__ __launch_bounds__(64) void core_reset_kernel(CoreStepArgs a, const uint8_t* mask) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);
@@ -1094,15 +1111,18 @@ __global__ __launch_bounds__(64) void core_reset_kernel(CoreStepArgs a, const ui
     }
     for (int i = threadIdx.x; i < a.F; i += 64) fl[i] = a.free_padded[i];
     wave_sync();
-    wave_reset_env(a, (uint32_t)(a.env_base + e), keys, fl, a.pos + e * a.A, threadIdx.x);
+    const int N = PEP ? a.envp[e].N : a.N;
+    wave_reset_env(a, (uint32_t)(a.env_base + e), keys, fl, a.pos + e * a.A, threadIdx.x, N,
+                   PEP ? a.envp[e].reset_thr : a.reset_thr);
     if (threadIdx.x == 0) {
-        a.cnt[e] = a.N;
+        a.cnt[e] = N;
         eplog_mark_start(a, e, a.t);
     }
 }
 
 // Reset every env of a map whose free list does not fit the wave reset's LDS
 // (big maps): one workgroup per env, keys in the env block's global scratch.
+template <bool PEP>
 __global__ __launch_bounds__(1024) void core_block_reset_kernel(CoreStepArgs a, const uint8_t* mask) {
     __shared__ int swsum[16];
     const long long e = blockIdx.x;
@@ -1114,9 +1134,9 @@ __global__ __launch_bounds__(1024) void core_block_reset_kernel(CoreStepArgs a, 
     }
     const BlockCarve cv = block_carve((a.H + 2) * (a.W + 2), a.A, 1, a.F, false, false, true, true);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(a.scratch + (size_t)e * a.scratch_stride + cv.keys);
-    block_place_env<1024>(a, e, keys, block_keys_cap(a.A, a.F), swsum);
+    block_place_env<1024, PEP>(a, e, keys, block_keys_cap(a.A, a.F), swsum);
     if (threadIdx.x == 0) {
-        a.cnt[e] = a.N;
+        a.cnt[e] = PEP ? a.envp[e].N : a.N;
         eplog_mark_start(a, e, a.t);
     }
 }
@@ -1134,6 +1154,30 @@ __global__ __launch_bounds__(256) void update_dff_kernel(const float* __restrict
     const int cell = (int)(c - e * HW);
     const int x = cell / W, y = cell - (cell / W) * W;
     const float* d = src + e * HW;
+    float acc = c0 * d[cell];
+#pragma unroll
+    for (int s = 0; s < NB; s++) {
+        const int nx = x + nb_dx<NB>(s), ny = y + nb_dy<NB>(s);
+        const float b = (nx >= 0 && nx < H && ny >= 0 && ny < W) ? c0 * d[nx * W + ny] : 0.0f;
+        const float t = c1 * b;
+        acc = acc + t;
+    }
+    dst[c] = acc < 1e-4f ? 0.0f : acc;
+}
+
+// The same with each env's own c0, c1 (per-env parameters).
+template <int NB>
+__global__ __launch_bounds__(256) void update_dff_env_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                             long long total, int H, int W,
+                                                             const EnvParams* __restrict__ envp) {
+    const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (c >= total) return;
+    const int HW = H * W;
+    const long long e = c / HW;
+    const int cell = (int)(c - e * HW);
+    const int x = cell / W, y = cell - (cell / W) * W;
+    const float* d = src + e * HW;
+    const float c0 = envp[e].c0, c1 = envp[e].c1;
     float acc = c0 * d[cell];
 #pragma unroll
     for (int s = 0; s < NB; s++) {
@@ -1202,26 +1246,31 @@ int core_wave_blocks_per_cu(const CoreStepArgs& a, int nb, bool mt) {
     return n;
 }
 
+size_t core_block_pep_smem_bytes(int K) { return (size_t)K * sizeof(EnvParams); }
+
+template <int NB, bool F64, bool MT, int BS, bool BIG>
+static hipError_t launch_block_bs(const CoreStepArgs& a, long long nblk, size_t smem, hipStream_t s) {
+    const dim3 gd((unsigned)nblk), bd(BS);
+    const bool epl = !MT && a.ep_start;
+    if (!MT && a.envp) {   // per-env parameters: the K records behind the carve
+        const size_t sp = smem + core_block_pep_smem_bytes(a.K);
+        if (sp > 64 * 1024) return hipErrorInvalidConfiguration;   // host-checked (ffm_engine_set_env_params)
+        if (epl) core_block_kernel<NB, F64, MT, BS, BIG, !MT, !MT><<<gd, bd, sp, s>>>(a);
+        else core_block_kernel<NB, F64, MT, BS, BIG, false, !MT><<<gd, bd, sp, s>>>(a);
+    } else if (epl) core_block_kernel<NB, F64, MT, BS, BIG, !MT, false><<<gd, bd, smem, s>>>(a);
+    else core_block_kernel<NB, F64, MT, BS, BIG, false, false><<<gd, bd, smem, s>>>(a);
+    return hipGetLastError();
+}
+
 template <int NB, bool F64, bool MT>
 static hipError_t launch_block_t(const CoreStepArgs& a, int block, hipStream_t s) {
     const long long nblk = (a.E + a.K - 1) / a.K;
-    if (a.scratch) {   // big maps: K = 1, state in global scratch
-        const size_t smem = block_carve((a.H + 2) * (a.W + 2), a.A, 1, a.F, F64, MT, true, true).lds;
-        if (!MT && a.ep_start)
-            core_block_kernel<NB, F64, MT, 1024, true, !MT><<<dim3((unsigned)nblk), dim3(1024), smem, s>>>(a);
-        else core_block_kernel<NB, F64, MT, 1024, true, false><<<dim3((unsigned)nblk), dim3(1024), smem, s>>>(a);
-        return hipGetLastError();
-    }
+    if (a.scratch)   // big maps: K = 1, state in global scratch
+        return launch_block_bs<NB, F64, MT, 1024, true>(
+            a, nblk, block_carve((a.H + 2) * (a.W + 2), a.A, 1, a.F, F64, MT, true, true).lds, s);
     const size_t smem = core_block_smem_bytes(a.H, a.W, a.A, a.K, a.F, F64, MT, !MT && a.auto_reset);
-    const bool epl = !MT && a.ep_start;
-    if (block == 512) {
-        if (epl) core_block_kernel<NB, F64, MT, 512, false, !MT><<<dim3((unsigned)nblk), dim3(512), smem, s>>>(a);
-        else core_block_kernel<NB, F64, MT, 512, false, false><<<dim3((unsigned)nblk), dim3(512), smem, s>>>(a);
-    } else {
-        if (epl) core_block_kernel<NB, F64, MT, 256, false, !MT><<<dim3((unsigned)nblk), dim3(256), smem, s>>>(a);
-        else core_block_kernel<NB, F64, MT, 256, false, false><<<dim3((unsigned)nblk), dim3(256), smem, s>>>(a);
-    }
-    return hipGetLastError();
+    if (block == 512) return launch_block_bs<NB, F64, MT, 512, false>(a, nblk, smem, s);
+    return launch_block_bs<NB, F64, MT, 256, false>(a, nblk, smem, s);
 }
 
 hipError_t launch_core_block(const CoreStepArgs& a, int nb, bool f64, bool mt, int block, hipStream_t s) {
@@ -1234,14 +1283,16 @@ hipError_t launch_core_block(const CoreStepArgs& a, int nb, bool f64, bool mt, i
 }
 
 hipError_t launch_core_block_reset(const CoreStepArgs& a, hipStream_t s, const uint8_t* mask) {
-    core_block_reset_kernel<<<dim3((unsigned)a.E), dim3(1024), 0, s>>>(a, mask);
+    if (a.envp) core_block_reset_kernel<true><<<dim3((unsigned)a.E), dim3(1024), 0, s>>>(a, mask);
+    else core_block_reset_kernel<false><<<dim3((unsigned)a.E), dim3(1024), 0, s>>>(a, mask);
     return hipGetLastError();
 }
 
 hipError_t launch_core_reset(const CoreStepArgs& a, hipStream_t s, const uint8_t* mask) {
     const size_t smem = align16((size_t)(a.F > 0 ? a.F : 1) * 8) + align16((size_t)(a.N > 0 ? a.N : 1) * 2) +
                         align16((size_t)(a.F > 0 ? a.F : 1) * 2);
-    core_reset_kernel<<<dim3((unsigned)a.E), dim3(64), smem, s>>>(a, mask);
+    if (a.envp) core_reset_kernel<true><<<dim3((unsigned)a.E), dim3(64), smem, s>>>(a, mask);
+    else core_reset_kernel<false><<<dim3((unsigned)a.E), dim3(64), smem, s>>>(a, mask);
     return hipGetLastError();
 }
 
@@ -1310,6 +1361,16 @@ hipError_t launch_update_dff(const float* src, float* dst, long long E, int H, i
     if (nblk == 0) return hipSuccess;
     if (nb == 4) update_dff_kernel<4><<<nblk, 256, 0, s>>>(src, dst, total, H, W, c0, c1);
     else update_dff_kernel<8><<<nblk, 256, 0, s>>>(src, dst, total, H, W, c0, c1);
+    return hipGetLastError();
+}
+
+hipError_t launch_update_dff_env(const float* src, float* dst, long long E, int H, int W, int nb,
+                                 const EnvParams* envp, hipStream_t s) {
+    const long long total = E * H * W;
+    const unsigned nblk = (unsigned)((total + 255) / 256);
+    if (nblk == 0) return hipSuccess;
+    if (nb == 4) update_dff_env_kernel<4><<<nblk, 256, 0, s>>>(src, dst, total, H, W, envp);
+    else update_dff_env_kernel<8><<<nblk, 256, 0, s>>>(src, dst, total, H, W, envp);
     return hipGetLastError();
 }
 

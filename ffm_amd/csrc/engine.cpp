@@ -104,7 +104,37 @@ struct ffm_engine {
     hipStream_t sh_stream[3] = {nullptr, nullptr, nullptr};   // shards 1..3
     hipEvent_t sh_fork = nullptr;
     hipEvent_t sh_end[3] = {nullptr, nullptr, nullptr};
+    // Per-env parameters (ffm_engine_set_env_params): null / empty while off.  While on, an
+    // engine of the group kernel steps with the lane kernel and one of the wave kernel with the
+    // block kernel (neither has a per-env form); the others keep their kernel.
+    ffm::EnvParams* d_envp = nullptr;          // [n_envs] records (kernels.h)
+    std::vector<ffm_env_params> pep_sets;      // the caller's tables, for ffm_engine_get_env_params
+    std::vector<int32_t> pep_set_of_env;
+    bool pep_lane = false;                     // step with the lane kernel
+    int pep_lane_blocks = 0;                   // its persistent grid
 };
+
+// The kernel that steps the engine under its current settings (per-env parameters move group and
+// wave engines): at most one of these holds, none means the block kernel.
+static bool steps_group(const ffm_engine* e) { return e->group && !e->d_envp; }
+static bool steps_lane(const ffm_engine* e) { return e->d_envp ? e->pep_lane : e->lane; }
+static bool steps_wave(const ffm_engine* e) { return e->wave && !e->d_envp; }
+static int lane_blocks_now(const ffm_engine* e) { return e->d_envp ? e->pep_lane_blocks : e->lane_blocks; }
+
+// The lane kernel's persistent grid for n_envs envs (a.envp set: of its per-env form).
+static int lane_grid(const ffm::CoreStepArgs& a, int nb, long long n_envs, int cus) {
+    const int per_cu = std::max(1, ffm::core_lane_blocks_per_cu(a, nb));
+    const long long groups = (n_envs + 1) / 2;
+    long long b = std::max<long long>(1, std::min<long long>((groups + 3) / 4, (long long)cus * per_cu));
+    if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {   // diagnostic override of the grid
+        const long long v = std::atoll(ov);
+        if (v > 0) b = std::min<long long>(v, (groups + 3) / 4);
+    }
+    // every wave steps at most core_lane_max_pairs_per_wave() pairs (its deferred
+    // reset mask); beyond that the grid grows past one resident wave of blocks
+    const long long per_wave = ffm::core_lane_max_pairs_per_wave();
+    return (int)std::max<long long>(b, (groups + 4 * per_wave - 1) / (4 * per_wave));
+}
 
 // Upper bound of FFM_STEP_SHARDS: the caller's stream + 3 of the engine's (a process has 4
 // hardware queues by default; more streams than queues only serialise).
@@ -169,6 +199,7 @@ static void release(ffm_engine* e) {
     (void)hipFree(e->d_mt_py);
     (void)hipFree(e->d_dbg);
     (void)hipFree(e->d_scratch);
+    (void)hipFree(e->d_envp);
     free_capture(e);
     free_episode_log(e, true);
     delete e;
@@ -343,19 +374,7 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
                 if (v > 0) e->wave_blocks = (int)std::min<long long>(v, (groups + 3) / 4);
             }
         }
-        if (e->lane) {
-            const int per_cu = std::max(1, ffm::core_lane_blocks_per_cu(a, d.neighborhood));
-            const long long groups = (d.n_envs + 1) / 2;
-            e->lane_blocks = (int)std::max<long long>(1, std::min<long long>((groups + 3) / 4, (long long)cus * per_cu));
-            if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {   // diagnostic override of the grid
-                const long long v = std::atoll(ov);
-                if (v > 0) e->lane_blocks = (int)std::min<long long>(v, (groups + 3) / 4);
-            }
-            // every wave steps at most core_lane_max_pairs_per_wave() pairs (its deferred
-            // reset mask); beyond that the grid grows past one resident wave of blocks
-            const long long per_wave = ffm::core_lane_max_pairs_per_wave();
-            e->lane_blocks = (int)std::max<long long>(e->lane_blocks, (groups + 4 * per_wave - 1) / (4 * per_wave));
-        }
+        if (e->lane) e->lane_blocks = lane_grid(a, d.neighborhood, d.n_envs, cus);
         if (e->multi) {
             const int per_cu = std::max(1, ffm::core_multi_blocks_per_cu(a, d.neighborhood));
             const long long pairs = (d.n_envs + 1) / 2;
@@ -537,14 +556,16 @@ static ffm::CoreStepArgs make_args(ffm_engine* e) {
     a.ephist = e->d_ephist;
     a.ephist_bins = e->ephist_bins;
     a.epsum = e->d_ephist ? e->d_ephist + ep_sum_offset(e->ephist_bins) : nullptr;
+    a.envp = e->d_envp;
     return a;
 }
 
 // Shards a step(n > 1) call runs as, under the engine's current settings: 1 (one launch per
 // step over all envs) with trajectory capture on (its kernel follows every step launch on the
-// caller's stream) and on the fused multi-step path.
+// caller's stream), on the fused multi-step path and with per-env parameters (the shards belong
+// to the group kernel).
 static int shards_in_effect(const ffm_engine* e) {
-    if (e->shards.size() <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi)) return 1;
+    if (e->shards.size() <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi) || e->d_envp) return 1;
     return (int)e->shards.size();
 }
 
@@ -618,9 +639,9 @@ int ffm_engine_step(ffm_engine* e, int32_t n_steps, void* stream) {
     }
     for (int i = 0; i < n_steps; i++) {
         ffm::CoreStepArgs a = make_args(e);
-        if (e->group) HIP_TRY(ffm::launch_core_group(a, e->d.neighborhood, e->group_blocks, s, e->group_g));
-        else if (e->lane) HIP_TRY(ffm::launch_core_lane(a, e->d.neighborhood, e->lane_blocks, s));
-        else if (e->wave) HIP_TRY(ffm::launch_core_wave(a, e->d.neighborhood, e->mt, e->wave_blocks, s));
+        if (steps_group(e)) HIP_TRY(ffm::launch_core_group(a, e->d.neighborhood, e->group_blocks, s, e->group_g));
+        else if (steps_lane(e)) HIP_TRY(ffm::launch_core_lane(a, e->d.neighborhood, lane_blocks_now(e), s));
+        else if (steps_wave(e)) HIP_TRY(ffm::launch_core_wave(a, e->d.neighborhood, e->mt, e->wave_blocks, s));
         else HIP_TRY(ffm::launch_core_block(a, e->d.neighborhood, e->f64, e->mt, e->block, s));
         if (e->cap.n_sel) HIP_TRY(ffm::launch_core_capture(a, e->cap, s));
         e->t++;
@@ -681,8 +702,12 @@ int ffm_engine_update_dff(ffm_engine* e, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)e->d.n_envs * e->HW;
     if (!e->d_tmp) HIP_TRY(hipMalloc((void**)&e->d_tmp, n * 4));
-    HIP_TRY(ffm::launch_update_dff(e->d_dff, e->d_tmp, e->d.n_envs, e->d.H, e->d.W, e->d.neighborhood, e->c0,
-                                   e->c1, s));
+    if (e->d_envp)
+        HIP_TRY(ffm::launch_update_dff_env(e->d_dff, e->d_tmp, e->d.n_envs, e->d.H, e->d.W, e->d.neighborhood,
+                                           e->d_envp, s));
+    else
+        HIP_TRY(ffm::launch_update_dff(e->d_dff, e->d_tmp, e->d.n_envs, e->d.H, e->d.W, e->d.neighborhood, e->c0,
+                                       e->c1, s));
     HIP_TRY(hipMemcpyAsync(e->d_dff, e->d_tmp, n * 4, hipMemcpyDeviceToDevice, s));
     return FFM_OK;
 }
@@ -934,6 +959,103 @@ int ffm_engine_get_episode_stats(ffm_engine* e, uint64_t* hist, int32_t bins, ui
     return FFM_OK;
 }
 
+int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t n_sets, const int32_t* set_of_env,
+                              void* stream) {
+    if (!e) return fail(FFM_E_INVALID, "null engine");
+    if (e->mt) return fail(FFM_E_UNSUPPORTED, "env params: Philox engines only");
+    if (n_sets < 0 || n_sets > e->d.n_envs) return fail(FFM_E_INVALID, "env params: n_sets must lie in [0, n_envs]");
+    hipStream_t s = (hipStream_t)stream;
+    if (n_sets == 0) {   // off: the create-time parameters, kernel and launch geometry
+        if (!e->d_envp) return FFM_OK;
+        HIP_TRY(hipStreamSynchronize(s));        // queued steps may still read the records
+        (void)hipFree(e->d_envp);
+        e->d_envp = nullptr;
+        e->pep_sets.clear();
+        e->pep_set_of_env.clear();
+        e->pep_lane = false;
+        e->pep_lane_blocks = 0;
+        return FFM_OK;
+    }
+    if (!sets || !set_of_env) return fail(FFM_E_INVALID, "env params: sets and set_of_env are required");
+    const int A = e->d.agent_capacity, nb = e->d.neighborhood;
+    for (int32_t p = 0; p < n_sets; p++) {
+        const ffm_env_params& q = sets[p];
+        if (!std::isfinite(q.k_S) || !std::isfinite(q.k_D) || !std::isfinite(q.diffuse) || !std::isfinite(q.decay))
+            return fail(FFM_E_INVALID, "env params: non-finite parameter");
+        if (q.n_agents < 1 || q.n_agents > std::min(A, e->F))
+            return fail(FFM_E_INVALID, "env params: n_agents must lie in [1, min(agent_capacity, free cells)]");
+    }
+    const size_t E = (size_t)e->d.n_envs;
+    for (size_t i = 0; i < E; i++)
+        if (set_of_env[i] < 0 || set_of_env[i] >= n_sets) return fail(FFM_E_INVALID, "env params: set_of_env out of range");
+    // The kernel while on.  Group engines: the lane kernel (the group kernel's conditions include
+    // the lane kernel's); wave engines, and whatever else is not on the lane kernel: the block kernel.
+    const bool lane = e->lane || (e->group && ffm::core_lane_smem_bytes(e->d.H, e->d.W, e->F, 4) <= 64 * 1024);
+    if (!lane && !e->big &&
+        ffm::core_block_smem_bytes(e->d.H, e->d.W, A, e->K, e->F, e->f64, false, e->d.auto_reset != 0) +
+                ffm::core_block_pep_smem_bytes(e->K) > 64 * 1024)
+        return fail(FFM_E_UNSUPPORTED, "env params: the block kernel's LDS has no room for the K records");
+    // The records, with the expressions of ffm_engine_create (the same bits as a homogeneous engine)
+    std::vector<ffm::EnvParams> rec(E);
+    const char* ov = std::getenv("FFM_RESET_CANDIDATES");
+    for (size_t i = 0; i < E; i++) {
+        const ffm_env_params& q = sets[set_of_env[i]];
+        ffm::EnvParams& r = rec[i];
+        r.kS32 = (float)(-q.k_S);
+        r.kD32 = (float)q.k_D;
+        r.kS64 = -q.k_S;
+        r.c0 = (float)((1.0 - q.decay) * (1.0 - q.diffuse));
+        r.c1 = (float)(q.decay * (1.0 - q.diffuse) / (double)nb);
+        r.N = q.n_agents;
+        const int N = q.n_agents, F = e->F;
+        int M = std::min(F, N + std::max(8, (N + 1) / 2));
+        if (ov) M = std::max(0, std::min(F, std::atoi(ov)));
+        r.reset_thr = M == 0 ? 0u : M == F ? 0xFFFFFFFFu : (uint32_t)(((uint64_t)M << 32) / (uint64_t)F);
+    }
+    HIP_TRY(hipSetDevice(e->d.device));
+    int lane_blocks = 0;
+    ffm::EnvParams* buf = e->d_envp;
+    if (!buf) {
+        hipError_t he = hipMalloc((void**)&buf, E * sizeof(ffm::EnvParams));
+        if (he != hipSuccess) return fail(FFM_E_NOMEM, std::string("env params: ") + hipGetErrorString(he));
+    }
+    auto undo = [&](int rc) {
+        if (!e->d_envp) (void)hipFree(buf);
+        return rc;
+    };
+    if (lane) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->d.device) != hipSuccess)
+            return undo(fail(FFM_E_HIP, "hipDeviceGetAttribute"));
+        ffm::CoreStepArgs a{};
+        a.H = e->d.H; a.W = e->d.W; a.A = A; a.F = e->F; a.auto_reset = e->d.auto_reset;
+        a.envp = buf;   // the occupancy of the per-env form
+        lane_blocks = lane_grid(a, nb, e->d.n_envs, cus);
+    }
+    // stream-ordered after the steps queued so far; the tables are consumed before the return
+    hipError_t he = hipMemcpyAsync(buf, rec.data(), E * sizeof(ffm::EnvParams), hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    if (he != hipSuccess) return undo(fail(FFM_E_HIP, std::string("env params: ") + hipGetErrorString(he)));
+    e->d_envp = buf;
+    e->pep_sets.assign(sets, sets + n_sets);
+    e->pep_set_of_env.assign(set_of_env, set_of_env + E);
+    e->pep_lane = lane;
+    e->pep_lane_blocks = lane_blocks;
+    return FFM_OK;
+}
+
+int ffm_engine_get_env_params(ffm_engine* e, ffm_env_params* sets, int32_t cap, int32_t* n_sets, int32_t* set_of_env) {
+    if (!e || !n_sets || cap < 0) return fail(FFM_E_INVALID, "null argument");
+    *n_sets = (int32_t)e->pep_sets.size();
+    if (*n_sets == 0) return FFM_OK;
+    if (sets) {
+        if (cap < *n_sets) return fail(FFM_E_INVALID, "get_env_params: buffer too small (*n_sets holds the count)");
+        std::copy(e->pep_sets.begin(), e->pep_sets.end(), sets);
+    }
+    if (set_of_env) std::copy(e->pep_set_of_env.begin(), e->pep_set_of_env.end(), set_of_env);
+    return FFM_OK;
+}
+
 int ffm_engine_get_counters(ffm_engine* e, uint64_t* counters, void* stream) {
     if (!e || !counters) return fail(FFM_E_INVALID, "null argument");
     hipStream_t s = (hipStream_t)stream;
@@ -997,7 +1119,8 @@ int ffm_debug_reset_candidates(ffm_engine* e, int32_t* m, uint32_t* thr) {
     return FFM_OK;
 }
 
-// Diagnostic (not part of the ABI header): the launch geometry chosen at create.
+// Diagnostic (not part of the ABI header): the launch geometry in effect (chosen at create; with
+// per-env parameters on, the kernel and grid that step the engine meanwhile).
 //   out[0] step kernel (0 group, 1 lane, 2 wave, 3 block, 4 block with global scratch)
 //   out[1] envs per group of the group kernel (0 for the other kernels)
 //   out[2] blocks of the step kernel's grid
@@ -1008,14 +1131,15 @@ int ffm_debug_reset_candidates(ffm_engine* e, int32_t* m, uint32_t* thr) {
 //          step over all envs), out[8] blocks of one shard's grid (the first's; out[2] if one shard)
 int ffm_debug_launch_info(ffm_engine* e, int32_t* out, int n) {
     if (!e || !out || n < 0 || n > 9) return fail(FFM_E_INVALID, "bad args");
-    const int kernel = e->group ? 0 : e->lane ? 1 : e->wave ? 2 : e->big ? 4 : 3;
+    const bool group = steps_group(e), lane = steps_lane(e), wave = steps_wave(e);
+    const int kernel = group ? 0 : lane ? 1 : wave ? 2 : e->big ? 4 : 3;
     const long long E = e->d.n_envs;
     const int S = shards_in_effect(e);
-    const int32_t step_blocks = e->group ? e->group_blocks : e->lane ? e->lane_blocks : e->wave ? e->wave_blocks
-                                                                                              : (int32_t)((E + e->K - 1) / e->K);
+    const int32_t step_blocks = group ? e->group_blocks : lane ? lane_blocks_now(e) : wave ? e->wave_blocks
+                                                                                        : (int32_t)((E + e->K - 1) / e->K);
     const int32_t v[9] = {
         kernel,
-        e->group ? e->group_g : 0,
+        group ? e->group_g : 0,
         step_blocks,
         e->K,
         kernel <= 2 ? 256 : e->big ? 1024 : e->block,

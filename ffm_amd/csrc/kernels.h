@@ -13,6 +13,18 @@ __host__ __device__ inline uint32_t magic_div(uint32_t d) { return (uint32_t)((0
 // every n < n_end divides exactly by magic_div(d)
 __host__ __device__ inline bool magic_div_ok(uint64_t n_end, uint32_t d) { return n_end * (uint64_t)d <= 0x100000000ull; }
 
+// Per-env parameters (ffm_engine_set_env_params): one 32-byte record per env, built on the host
+// from the env's set with the expressions ffm_engine_create uses for the engine-wide values, so
+// an env steps bit for bit like a homogeneous engine of its set.
+struct EnvParams {
+    float kS32, kD32;      // f32(-k_S), f32(k_D)
+    float c0, c1;          // f32((1-decay)(1-diffuse)), f32(decay(1-diffuse)/|nb|)
+    double kS64;           // -k_S (float64 SFF path)
+    int N;                 // agents placed at the env's next placement
+    uint32_t reset_thr;    // CoreStepArgs::reset_thr for this N
+};
+static_assert(sizeof(EnvParams) == 32, "EnvParams is one 32-byte record");
+
 struct CoreStepArgs {
     int H, W, HW;          // map shape
     uint32_t mW, mPW;      // magic_div(W), magic_div(W + 2): row of a cell index by one multiply-high
@@ -63,6 +75,9 @@ struct CoreStepArgs {
     unsigned long long* epsum;     // [kEpSumSlots][kEpSumStride] partial summaries (with ephist): count, sum of
                                    // steps, sum of steps^2, max of ~steps (the min, inverted: zero is its empty
                                    // value), max; an env adds to slot e % kEpSumSlots, the host sums the slots
+    // Per-env parameters: [E] records, or nullptr (off: kS32 .. c1, N and reset_thr above hold for
+    // every env).  The launchers pick the kernels' PEP instantiations when it is set.
+    const EnvParams* envp;
 };
 
 // The summary is spread over slots of one 128-byte line each: a single contended word takes
@@ -112,6 +127,11 @@ size_t core_big_scratch_bytes(int H, int W, int A, int F, bool mt);
 hipError_t launch_core_block_reset(const CoreStepArgs& a, hipStream_t s, const uint8_t* mask = nullptr);
 hipError_t launch_update_dff(const float* src, float* dst, long long E, int H, int W, int nb, float c0,
                              float c1, hipStream_t s);
+// the same with each env's own c0, c1 (envp: [E] records)
+hipError_t launch_update_dff_env(const float* src, float* dst, long long E, int H, int W, int nb,
+                                 const EnvParams* envp, hipStream_t s);
+// extra LDS of the block kernel's PEP form (the K staged records)
+size_t core_block_pep_smem_bytes(int K);
 hipError_t launch_core_capture_init(const CoreStepArgs& a, const CoreCapture& c, hipStream_t s);
 hipError_t launch_core_capture(const CoreStepArgs& a, const CoreCapture& c, hipStream_t s);
 hipError_t launch_np_expf(const float* x, float* y, long long n, hipStream_t s);

@@ -25,11 +25,13 @@ __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, i
 // divisions by F and PW are loop invariants the compiler otherwise sets up in every wave of a
 // kernel that holds this call in a loop, whether or not an env is re-placed.
 // CAND: the small-list path first tries the candidate pass below (a.reset_thr, set at create).
+// N, thr: the agents placed and the candidate threshold -- a.N and a.reset_thr, or the env's own
+// (per-env parameters, kernels.h EnvParams).
 template <int PWK = 0, bool SMALL = false, bool CAND = true>
 __device__ inline void wave_reset_env(const CoreStepArgs& a, uint32_t genv, unsigned long long* keys, const uint16_t* fl,
-                               uint16_t* gpos, int lane) {
+                               uint16_t* gpos, int lane, int N, uint32_t thr) {
     const int PW = PWK > 0 ? PWK : a.W + 2;
-    const int F = a.F, N = a.N;
+    const int F = a.F;
     if (SMALL || F <= 128) {
         // lane holds keys j0 = lane and j1 = lane + 64 and ranks both in one pass over
         // 16-B broadcast reads of the key list (two keys per read; keys is 16-B aligned)
@@ -49,7 +51,7 @@ __device__ inline void wave_reset_env(const CoreStepArgs& a, uint32_t genv, unsi
             // lane i ranks the one word keys[i] over (C + 1) / 2 reads.  C outside [N, 64] (about
             // one placement in 1,150 at F = 100, N = 32), or reset_thr = 0: the full ranking below.
             // A pad lane's ~0 key is never below reset_thr.
-            const bool c0 = (uint32_t)(k0 >> 32) < a.reset_thr, c1 = (uint32_t)(k1 >> 32) < a.reset_thr;
+            const bool c0 = (uint32_t)(k0 >> 32) < thr, c1 = (uint32_t)(k1 >> 32) < thr;
             const unsigned long long m0 = __ballot(c0), m1 = __ballot(c1);
             const int C0 = __popcll(m0), C = C0 + __popcll(m1);
             if (C >= N && C <= 64) {
@@ -116,6 +118,13 @@ __device__ inline void wave_reset_env(const CoreStepArgs& a, uint32_t genv, unsi
         if (rank < N) gpos[rank] = (uint16_t)unpad(fl[(int)(ki & 0xFFFFu)], PW);
     }
     wave_sync();
+}
+
+// The engine-wide form: a.N agents, a.reset_thr.
+template <int PWK = 0, bool SMALL = false, bool CAND = true>
+__device__ inline void wave_reset_env(const CoreStepArgs& a, uint32_t genv, unsigned long long* keys, const uint16_t* fl,
+                               uint16_t* gpos, int lane) {
+    wave_reset_env<PWK, SMALL, CAND>(a, genv, keys, fl, gpos, lane, a.N, a.reset_thr);
 }
 
 }  // namespace ffm

@@ -31,6 +31,7 @@ EXPORTED = [
     "ffm_engine_set_trajectory_capture", "ffm_engine_drain_trajectory",
     "ffm_engine_set_episode_log", "ffm_engine_drain_episodes", "ffm_engine_get_episode_stats",
     "ffm_debug_stage_image", "ffm_debug_reset_candidates",
+    "ffm_engine_set_env_params", "ffm_engine_get_env_params",
     "ffm_learner_create", "ffm_learner_destroy", "ffm_learner_reset", "ffm_learner_reset_envs", "ffm_learner_step",
     "ffm_learner_set_state", "ffm_learner_get_state", "ffm_learner_get_episodes",
     "ffm_learner_set_mt_state", "ffm_learner_get_mt_state", "ffm_learner_get_counters",
@@ -66,6 +67,17 @@ class EngineDesc(C.Structure):
         ("rng_mode", C.c_int32), ("auto_reset", C.c_int32), ("seed", C.c_uint64),
         ("env_base", C.c_int64), ("device", C.c_int32), ("envs_per_block", C.c_int32),
     ]
+
+
+class EnvParams(C.Structure):
+    """ffm_env_params: one parameter set of ffm_engine_set_env_params."""
+    _fields_ = [
+        ("k_S", C.c_double), ("k_D", C.c_double), ("diffuse", C.c_double), ("decay", C.c_double),
+        ("n_agents", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+ENV_PARAM_KEYS = ("k_S", "k_D", "diffuse", "decay", "n_agents")
 
 
 class LearnDesc(C.Structure):
@@ -137,6 +149,8 @@ def load_library():
     L.ffm_engine_set_episode_log.argtypes = [P, i64, i32, P]
     L.ffm_engine_drain_episodes.argtypes = [P, P, i64, C.POINTER(i64), C.POINTER(i64), P]
     L.ffm_engine_get_episode_stats.argtypes = [P, P, i32, P, i32, P]
+    L.ffm_engine_set_env_params.argtypes = [P, C.POINTER(EnvParams), i32, P, P]
+    L.ffm_engine_get_env_params.argtypes = [P, C.POINTER(EnvParams), i32, C.POINTER(i32), P]
     L.ffm_np_expf_device.argtypes = [P, P, i64, P]
     L.ffm_debug_stage_image.argtypes = [P, P, i64, C.POINTER(i64)]
     L.ffm_debug_reset_candidates.argtypes = [P, C.POINTER(i32), C.POINTER(C.c_uint32)]
@@ -352,6 +366,50 @@ class Engine:
     def update_dff(self, stream=None):
         _check(self._L.ffm_engine_update_dff(self._h, _stream_handle(stream)))
 
+    # -- per-env parameters ----------------------------------------------------
+    def set_env_params(self, sets, set_of_env=None, stream=None):
+        """A sweep in one engine (ffm_engine_set_env_params): env e takes sets[set_of_env[e]] and
+        from the next step on evolves bit for bit like the env with the same global id of an
+        engine created with that set.  `sets`: dicts with any of k_S, k_D, diffuse, decay,
+        n_agents (missing keys: the engine's create-time values); `set_of_env`: n_envs indices
+        into it (default arange(n_envs) % len(sets)).  A new n_agents holds from the env's next
+        placement (reset, reset_envs, auto-reset).  sets=None or []: off -- back to the
+        create-time parameters, kernel and launch geometry.  While on, a "group" engine steps
+        with the lane kernel and a "wave" engine with the block kernel (launch_info())."""
+        sets = list(sets) if sets is not None else []
+        if not sets:
+            _check(self._L.ffm_engine_set_env_params(self._h, None, 0, None, _stream_handle(stream)))
+            return
+        base = {"k_S": self.params["k_S"], "k_D": self.params["k_D"], "diffuse": self.params["diffuse"],
+                "decay": self.params["decay"], "n_agents": self.n_agents}
+        arr = (EnvParams * len(sets))()
+        for q, st in zip(arr, sets):
+            unknown = set(st) - set(ENV_PARAM_KEYS)
+            if unknown:
+                raise ValueError(f"unknown env parameter(s) {sorted(unknown)}; known: {ENV_PARAM_KEYS}")
+            v = {**base, **st}
+            q.k_S, q.k_D, q.diffuse, q.decay = float(v["k_S"]), float(v["k_D"]), float(v["diffuse"]), float(v["decay"])
+            q.n_agents = int(v["n_agents"])
+        if set_of_env is None:
+            soe = (np.arange(self.n_envs) % len(sets)).astype(np.int32)
+        else:
+            soe = np.ascontiguousarray(set_of_env, dtype=np.int32).reshape(-1)
+            if soe.size != self.n_envs:
+                raise ValueError(f"set_of_env must have n_envs = {self.n_envs} entries, got {soe.size}")
+        _check(self._L.ffm_engine_set_env_params(self._h, arr, len(sets), _ptr(soe), _stream_handle(stream)))
+
+    def env_params(self):
+        """(sets, set_of_env) in effect (ffm_engine_get_env_params): a list of dicts and an int32
+        array [n_envs]; ([], None) while the feature is off."""
+        n = C.c_int32()
+        _check(self._L.ffm_engine_get_env_params(self._h, None, 0, C.byref(n), None))
+        if n.value == 0:
+            return [], None
+        arr = (EnvParams * n.value)()
+        soe = np.empty(self.n_envs, np.int32)
+        _check(self._L.ffm_engine_get_env_params(self._h, arr, n.value, C.byref(n), _ptr(soe)))
+        return [{k: getattr(q, k) for k in ENV_PARAM_KEYS} for q in arr], soe
+
     # -- episode I/O ---------------------------------------------------------
     def set_trajectory_capture(self, envs, period: int = 1, phases=None, capacity_rows: int | None = None,
                                stream=None):
@@ -562,7 +620,8 @@ class Engine:
         return {k: b.__getattribute__(k) for k, _ in DeviceBuffers._fields_}
 
     def launch_info(self) -> dict:
-        """The launch geometry chosen at create (diagnostic, ffm_debug_launch_info): the step
+        """The launch geometry in effect (chosen at create; with per-env parameters on, the kernel
+        and grid that step the engine meanwhile; diagnostic, ffm_debug_launch_info): the step
         kernel ("group", "lane", "wave", "block" or "block_scratch"), the group kernel's envs per
         group (0 for the other kernels), the step grid's blocks, the block kernel's envs per
         workgroup K, the block size, the fused multi-step kernel's availability and grid, and the

@@ -12,25 +12,100 @@ the same).  This driver runs ``--envs`` independent replicas of that loop on one
 
     python -m ffm_amd.evac --room 12 12 --N 32 --envs 4096 --episodes 4 --out runs/evac
     python -m ffm_amd.evac --map map.npy --sff sff.npy --N 50 --envs 1024 --out runs/evac
+
+A sweep runs in the same engine (``Engine.set_env_params``): ``--sweep NAME=v1,v2,...``
+(repeatable; NAME one of k_S k_D diffuse decay N) makes the Cartesian product of the lists, in
+argument order, the parameter sets; env e runs set e % P, so every wave mixes long and short
+episodes.  ``steps_per_episode.csv`` then carries each env's own N and gains the columns
+``k_S,k_D,diffuse,decay`` (``analyze_steps_by_n.py`` reads an N sweep directly), and
+``sweep_summary.csv`` has one row per set: parameters, count, mean, std, min, max.
+
+    python -m ffm_amd.evac --room 12 12 --sweep N=5,10,20,32 --sweep k_D=0,1,4 --envs 4096 --out runs/sweep
 """
 from __future__ import annotations
 
 import argparse
+import itertools
 import os
 import time
 
 import numpy as np
 
 
-def steps_csv(records: np.ndarray, episodes: int, N: int) -> str:
+SWEEP_NAMES = ("k_S", "k_D", "diffuse", "decay", "N")
+
+
+def parse_sweep(text: str):
+    """``NAME=v1,v2,...`` -> (NAME, [values]); N values are ints, the others floats."""
+    name, sep, vals = text.partition("=")
+    name = name.strip()
+    if not sep or name not in SWEEP_NAMES:
+        raise ValueError(f"--sweep wants NAME=v1,v2,... with NAME one of {' '.join(SWEEP_NAMES)}: {text!r}")
+    items = [v for v in vals.split(",") if v.strip()]
+    if not items:
+        raise ValueError(f"--sweep {name}: no values")
+    return name, [int(v) if name == "N" else float(v) for v in items]
+
+
+def sweep_grid(sweeps, base: dict) -> list:
+    """The parameter sets of a sweep: the Cartesian product of the (name, values) lists in
+    argument order (the first name varies slowest), every other parameter from `base`.  Each
+    set is a dict with the keys k_S, k_D, diffuse, decay, N."""
+    names = [n for n, _ in sweeps]
+    if len(set(names)) != len(names):
+        raise ValueError("--sweep: a name is given twice")
+    sets = []
+    for combo in itertools.product(*[v for _, v in sweeps]):
+        st = {k: base[k] for k in SWEEP_NAMES}
+        st.update(zip(names, combo))
+        sets.append(st)
+    return sets
+
+
+def env_assignment(n_envs: int, n_sets: int) -> np.ndarray:
+    """Env e runs set e % P."""
+    if n_envs < n_sets:
+        raise ValueError(f"--envs must be at least the number of sets ({n_sets})")
+    return (np.arange(n_envs) % n_sets).astype(np.int32)
+
+
+def _num(v) -> str:
+    return f"{v:g}" if isinstance(v, float) else str(v)
+
+
+def steps_csv(records: np.ndarray, episodes: int, N: int, sets=None, set_of_env=None, env_base: int = 0) -> str:
     """The text of steps_per_episode.csv from episode records [n, 4] int32 {env, episode
     index k, steps, t_end} (Engine.drain_episodes): one row per record in (env, k) order,
-    episode_num = env * episodes + k + 1."""
+    episode_num = env * episodes + k + 1.  With `sets` (sweep_grid) and `set_of_env` the N
+    column carries the env's own N and the columns k_S, k_D, diffuse, decay follow."""
     rec = np.asarray(records, dtype=np.int64).reshape(-1, 4)
     rec = rec[np.lexsort((rec[:, 1], rec[:, 0]))]
-    lines = ["episode_num,env,N,steps"]
+    if sets is None:
+        lines = ["episode_num,env,N,steps"]
+        for env, k, steps, _ in rec.tolist():
+            lines.append(f"{env * episodes + k + 1},{env},{N},{steps}")
+        return "\n".join(lines) + "\n"
+    lines = ["episode_num,env,N,steps,k_S,k_D,diffuse,decay"]
     for env, k, steps, _ in rec.tolist():
-        lines.append(f"{env * episodes + k + 1},{env},{N},{steps}")
+        st = sets[int(set_of_env[env - env_base])]
+        lines.append(f"{env * episodes + k + 1},{env},{st['N']},{steps}," +
+                     ",".join(_num(st[c]) for c in ("k_S", "k_D", "diffuse", "decay")))
+    return "\n".join(lines) + "\n"
+
+
+def sweep_summary_csv(steps: np.ndarray, sets, set_of_env) -> str:
+    """The text of sweep_summary.csv: one row per set with its parameters and the count, mean,
+    std, min, max of the evacuation times [E, per_env] of its envs."""
+    steps = np.asarray(steps)
+    soe = np.asarray(set_of_env)
+    lines = ["set,k_S,k_D,diffuse,decay,N,count,mean,std,min,max"]
+    for p, st in enumerate(sets):
+        s = steps[soe == p].astype(np.float64).reshape(-1)
+        head = f"{p}," + ",".join(_num(st[c]) for c in ("k_S", "k_D", "diffuse", "decay", "N"))
+        if s.size == 0:
+            lines.append(head + ",0,nan,nan,0,0")
+        else:
+            lines.append(head + f",{s.size},{s.mean():.6f},{s.std():.6f},{int(s.min())},{int(s.max())}")
     return "\n".join(lines) + "\n"
 
 
@@ -65,6 +140,8 @@ def main(argv=None):
     ap.add_argument("--decay", type=float, default=0.2)
     ap.add_argument("--neighborhood", choices=("neumann", "moore"), default="moore")
     ap.add_argument("--max-steps", type=int, default=None)
+    ap.add_argument("--sweep", action="append", default=[], metavar="NAME=v1,v2,...",
+                    help="sweep k_S, k_D, diffuse, decay or N in one engine (repeatable: Cartesian product)")
     ap.add_argument("--out", required=True, metavar="DIR")
     a = ap.parse_args(argv)
     if bool(a.map) != bool(a.sff) or bool(a.map) == bool(a.room):
@@ -78,8 +155,20 @@ def main(argv=None):
     else:
         m, sff = np.load(a.map), np.load(a.sff)
     params = {"k_S": a.k_S, "k_D": a.k_D, "diffuse": a.diffuse, "decay": a.decay, "neighborhood": a.neighborhood}
-    eng = Engine(m, sff, n_envs=a.envs, n_agents=a.N, params=params, rng="philox", seed=a.seed,
+    sets = soe = None
+    n_max = a.N
+    if a.sweep:
+        try:
+            sets = sweep_grid([parse_sweep(t) for t in a.sweep], {**params, "N": a.N})
+            soe = env_assignment(a.envs, len(sets))
+        except ValueError as err:
+            ap.error(str(err))
+        n_max = max(st["N"] for st in sets)   # the agent capacity
+    eng = Engine(m, sff, n_envs=a.envs, n_agents=n_max, params=params, rng="philox", seed=a.seed,
                  auto_reset=a.episodes > 1)
+    if sets:   # before the reset: its placement takes each env's own N
+        eng.set_env_params([{"k_S": st["k_S"], "k_D": st["k_D"], "diffuse": st["diffuse"], "decay": st["decay"],
+                             "n_agents": st["N"]} for st in sets], soe)
     eng.set_episode_log(hist_bins=0)
     eng.reset()
     t0 = time.perf_counter()
@@ -90,7 +179,10 @@ def main(argv=None):
 
     os.makedirs(a.out, exist_ok=True)
     with open(os.path.join(a.out, "steps_per_episode.csv"), "w") as f:
-        f.write(steps_csv(records_from_steps(steps), a.episodes, a.N))
+        f.write(steps_csv(records_from_steps(steps), a.episodes, a.N, sets, soe))
+    if sets:
+        with open(os.path.join(a.out, "sweep_summary.csv"), "w") as f:
+            f.write(sweep_summary_csv(steps, sets, soe))
     text = summary_text(steps, taken * a.envs, dt)
     with open(os.path.join(a.out, "summary.txt"), "w") as f:
         f.write(text)

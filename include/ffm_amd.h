@@ -218,6 +218,49 @@ int ffm_engine_drain_episodes(ffm_engine* eng, int32_t* records, int64_t cap, in
 int ffm_engine_get_episode_stats(ffm_engine* eng, uint64_t* hist, int32_t bins, uint64_t* summary, int32_t clear,
                                  void* stream);
 
+/* Per-env parameters and agent counts: a whole sweep in one engine.  Replaces the user's loop
+ * over FloorFieldModel(params=...) instances, one per point of an evacuation-time-against-N
+ * curve (analyze_steps_by_n.py) or of the (k_S, k_D) plane -- each far too small to fill the
+ * GPU, each with its own create and host loop -- by one engine and one launch per step.
+ *
+ * Env e (global id env_base + e) takes sets[set_of_env[e]] and from then on evolves bit for
+ * bit like the env with the same global id of a homogeneous engine created with that set's
+ * k_S, k_D, diffuse, decay and n_agents and the same map, SFF, neighbourhood, seed, auto_reset
+ * and step indices: positions, counts, DFF bits, episodes and episode-log records.  (Every
+ * Philox draw is keyed by (seed, t, global env, agent, purpose); the placement takes the
+ * n_agents smallest of keys that do not depend on n_agents.)
+ *
+ * 1 <= n_sets <= n_envs; set_of_env is a host array [n_envs] of indices into sets.
+ * n_sets = 0 turns the feature off: the engine goes back to its create-time parameters,
+ * kernel and launch geometry, and the per-env buffer is freed (sets, set_of_env ignored).
+ * May be called between steps at any time; stream-ordered on `stream`, the tables are copied
+ * before it returns (it synchronises the stream).  Parameters take effect from the next step;
+ * a new n_agents at the env's next placement (ffm_engine_reset, ffm_engine_reset_envs or the
+ * auto-reset).  Episode indices and the episode log's start indices are untouched.
+ * ffm_engine_update_dff uses each env's diffuse / decay.  Trajectory capture, the episode
+ * log and fused steps work unchanged.
+ *
+ * Validated before anything changes: 1 <= n_agents <= min(agent_capacity, free cells),
+ * finite parameters, set_of_env entries in [0, n_sets), non-null tables: FFM_E_INVALID.
+ * MT engines: FFM_E_UNSUPPORTED.
+ *
+ * Kernels: the group kernel (12x12 default) and the wave kernel have no per-env form yet.
+ * While the feature is on, a group engine steps with the lane kernel and a wave engine with
+ * the block kernel (step shards, which belong to the group kernel, are off); both return to
+ * their own kernel at n_sets = 0.  Lane, fused and block engines keep theirs.  (A block
+ * engine whose LDS has no 32 bytes per env of its workgroup left: FFM_E_UNSUPPORTED.) */
+typedef struct {
+    double k_S, k_D, diffuse, decay;
+    int32_t n_agents;
+    int32_t reserved;
+} ffm_env_params;
+int ffm_engine_set_env_params(ffm_engine* eng, const ffm_env_params* sets, int32_t n_sets,
+                              const int32_t* set_of_env /* host [n_envs] */, void* stream);
+/* The tables in effect: *n_sets = 0 while off.  sets (cap entries) and set_of_env ([n_envs])
+ * may be NULL; cap < *n_sets: FFM_E_INVALID with *n_sets = count needed. */
+int ffm_engine_get_env_params(ffm_engine* eng, ffm_env_params* sets, int32_t cap, int32_t* n_sets,
+                              int32_t* set_of_env /* host [n_envs] or NULL */);
+
 /* counters[4] = {agent_steps, exits, resets, steps} accumulated since create. */
 int ffm_engine_get_counters(ffm_engine* eng, uint64_t* counters, void* stream);
 int ffm_engine_device_buffers(ffm_engine* eng, ffm_device_buffers* out);
