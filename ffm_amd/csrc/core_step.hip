@@ -1302,10 +1302,14 @@ hipError_t launch_core_reset(const CoreStepArgs& a, hipStream_t s, const uint8_t
 // moved during the step was emptied by it (and re-placed by the auto-reset): its row is
 // the empty row that ended the logged episode.  An env that was already empty (no
 // auto-reset) logs nothing.
-__global__ __launch_bounds__(64) void core_capture_init_kernel(CoreStepArgs a, CoreCapture c) {
+// mask (ffm_engine_reset_envs, after its placement): only the selected envs with a nonzero
+// byte restart -- steps from 0 and the last-seen count from the new placement, so an env that
+// had emptied logs again; their episode index is the one they had.
+__global__ __launch_bounds__(64) void core_capture_init_kernel(CoreStepArgs a, CoreCapture c, const uint8_t* mask) {
     const int i = (int)(blockIdx.x * 64 + threadIdx.x);
     if (i >= c.n_sel) return;
     const long long e = c.envs[i];
+    if (mask && !mask[e]) return;
     c.state[3 * i] = a.episodes[e];
     c.state[3 * i + 1] = 0;
     c.state[3 * i + 2] = a.cnt[e];
@@ -1344,8 +1348,8 @@ __global__ __launch_bounds__(64) void core_capture_kernel(CoreStepArgs a, CoreCa
     }
 }
 
-hipError_t launch_core_capture_init(const CoreStepArgs& a, const CoreCapture& c, hipStream_t s) {
-    core_capture_init_kernel<<<dim3((unsigned)((c.n_sel + 63) / 64)), dim3(64), 0, s>>>(a, c);
+hipError_t launch_core_capture_init(const CoreStepArgs& a, const CoreCapture& c, hipStream_t s, const uint8_t* mask) {
+    core_capture_init_kernel<<<dim3((unsigned)((c.n_sel + 63) / 64)), dim3(64), 0, s>>>(a, c, mask);
     return hipGetLastError();
 }
 

@@ -694,6 +694,9 @@ int ffm_engine_reset_envs(ffm_engine* e, const uint8_t* mask, void* stream) {
         HIP_TRY(ffm::launch_core_reset(make_args(e), s, mask));
     }
     e->t++;
+    // trajectory capture: the masked envs' rows count from this placement (same episode index),
+    // and one that had emptied logs again; nothing is launched while capture is off
+    if (e->cap.n_sel) HIP_TRY(ffm::launch_core_capture_init(make_args(e), e->cap, s, mask));
     return FFM_OK;
 }
 

@@ -132,7 +132,9 @@ hipError_t launch_update_dff_env(const float* src, float* dst, long long E, int 
                                  const EnvParams* envp, hipStream_t s);
 // extra LDS of the block kernel's PEP form (the K staged records)
 size_t core_block_pep_smem_bytes(int K);
-hipError_t launch_core_capture_init(const CoreStepArgs& a, const CoreCapture& c, hipStream_t s);
+// mask: nullptr = every selected env; else ([E] device bytes) only those with a nonzero byte
+hipError_t launch_core_capture_init(const CoreStepArgs& a, const CoreCapture& c, hipStream_t s,
+                                    const uint8_t* mask = nullptr);
 hipError_t launch_core_capture(const CoreStepArgs& a, const CoreCapture& c, hipStream_t s);
 hipError_t launch_np_expf(const float* x, float* y, long long n, hipStream_t s);
 

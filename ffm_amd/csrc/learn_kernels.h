@@ -143,7 +143,8 @@ struct LearnArgs {
     long long tsrc;             // 0: back to back.  tsrc: records between two ranges' blocks (tblk when 0)
     int ow, orank, ochunk;
     // owner mode outputs: the V values the launch's tiles updated (slot, new value) and the
-    // H increments (slot | action << 28, fixed-point sum), appended for the other ranks
+    // H increments (slot & kHoutSlot | action << kHoutActShift | kHoutNew on a new row's first
+    // entry, fixed-point sum), appended for the other ranks
     uint32_t* vout_slot;
     double* vout_val;
     unsigned long long* vout_n;

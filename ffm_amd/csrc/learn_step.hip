@@ -4177,6 +4177,8 @@ constexpr int kResetBS = 256;
 constexpr int kResetCap = 16384;
 constexpr int kResetBin = 256;    // keys of one histogram bin (the exact-threshold fallback)
 
+// TAIL (a masked reset, all == 2): the row's slots behind the new count are cleared as well.
+template <bool TAIL = false>
 __device__ __forceinline__ void reset_env(const LearnArgs& a, int all, long long e) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);
@@ -4292,6 +4294,10 @@ __device__ __forceinline__ void reset_env(const LearnArgs& a, int all, long long
         }
         NN += need < hb ? need : hb;
     }
+    // a masked reset leaves no cell of the abandoned episode behind the new count (as
+    // ffm_learner_reset's memset; the steps' own re-placement promises no tail)
+    if (TAIL)
+        for (int r = NN + tid; r < a.A; r += kResetBS) a.pos[e * a.A + r] = kNone16;
     float* d = a.dff_in + e * (long long)a.HW;
     for (int c = tid; c < a.HW; c += kResetBS) d[c] = 0.0f;
     if (tid == 0) {
@@ -4306,8 +4312,9 @@ __device__ __forceinline__ void reset_env(const LearnArgs& a, int all, long long
     }
 }
 
+template <bool TAIL>
 __global__ __launch_bounds__(kResetBS) void learn_reset_kernel(LearnArgs a, int all) {
-    reset_env(a, all, (long long)blockIdx.x);
+    reset_env<TAIL>(a, all, (long long)blockIdx.x);
 }
 
 // The H statistics' final reduction (workgroup 0) and the re-placement of the ended envs
@@ -4405,7 +4412,8 @@ __device__ __forceinline__ void lwave_sync() {
 // One wave re-places its ended envs among [e0, e0 + kResetSmallEnvs), keys in its own LDS
 // row.  WAVE: the wave shares its workgroup with others (learn_apply_vh_kernel), so it
 // synchronises itself only.
-template <bool WAVE>
+// TAIL: as reset_env's.
+template <bool WAVE, bool TAIL = false>
 __device__ __forceinline__ void reset_small_wave(const LearnArgs& a, int all, long long e0, unsigned long long* keys) {
     const int lane = (int)(threadIdx.x & 63);
     const long long me = e0 + lane;
@@ -4448,6 +4456,8 @@ __device__ __forceinline__ void reset_small_wave(const LearnArgs& a, int all, lo
             const int j = lane + 64 * q;
             if (j < F && rank[q] < N) a.pos[e * a.A + rank[q]] = a.free_cells[j];
         }
+        if (TAIL)       // a masked reset: no cell of the abandoned episode behind the new count
+            for (int j = N + lane; j < a.A; j += 64) a.pos[e * a.A + j] = kNone16;
         float* d = a.dff_in + e * (long long)HW;
         for (int c = lane; c < HW; c += 64) d[c] = 0.0f;
         if (lane == 0) {
@@ -4464,9 +4474,10 @@ __device__ __forceinline__ void reset_small_wave(const LearnArgs& a, int all, lo
     }
 }
 
+template <bool TAIL>
 __global__ __launch_bounds__(64) void learn_reset_small_kernel(LearnArgs a, int all) {
     __shared__ __attribute__((aligned(16))) unsigned long long keys[kResetSmallF + 2];
-    reset_small_wave<false>(a, all, (long long)blockIdx.x * kResetSmallEnvs, keys);
+    reset_small_wave<false, TAIL>(a, all, (long long)blockIdx.x * kResetSmallEnvs, keys);
 }
 
 // nbr > 0: the last nbr workgroups re-place the ended envs as well (ra: the step's
@@ -5047,22 +5058,29 @@ hipError_t launch_learn_reset_mask(const LearnArgs& a, const uint8_t* mask, hipS
     return e != hipSuccess ? e : launch_learn_reset(a, 2, s);
 }
 
-hipError_t launch_learn_reset(const LearnArgs& a, int all, hipStream_t s) {
+// TAIL: the masked reset's build of the two placement kernels (the slots behind the new count
+// cleared); the steps' and reset()'s build is the one without.
+template <bool TAIL>
+static hipError_t launch_learn_reset_t(const LearnArgs& a, int all, hipStream_t s) {
     if (a.F <= kResetSmallF && a.N <= a.F) {
-        learn_reset_small_kernel<<<dim3((unsigned)((a.E + kResetSmallEnvs - 1) / kResetSmallEnvs)), dim3(64), 0, s>>>(
-            a, all);
+        learn_reset_small_kernel<TAIL>
+            <<<dim3((unsigned)((a.E + kResetSmallEnvs - 1) / kResetSmallEnvs)), dim3(64), 0, s>>>(a, all);
         return hipGetLastError();
     }
     int P = 1;
     while (P < (a.F < kResetCap ? a.F : kResetCap)) P <<= 1;
     const size_t smem = (size_t)P * 8;
     if (smem > 65536) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&learn_reset_kernel),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&learn_reset_kernel<TAIL>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return e;
     }
-    learn_reset_kernel<<<dim3((unsigned)a.E), dim3(kResetBS), smem, s>>>(a, all);
+    learn_reset_kernel<TAIL><<<dim3((unsigned)a.E), dim3(kResetBS), smem, s>>>(a, all);
     return hipGetLastError();
+}
+
+hipError_t launch_learn_reset(const LearnArgs& a, int all, hipStream_t s) {
+    return all == 2 ? launch_learn_reset_t<true>(a, all, s) : launch_learn_reset_t<false>(a, all, s);
 }
 
 hipError_t launch_learn_delta_export(const LearnTable& T, int width, unsigned long long* keys, long long* acc,

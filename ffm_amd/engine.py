@@ -239,15 +239,26 @@ def _stream_handle(stream):
     return int(getattr(stream, "cuda_stream"))
 
 
-def _device_mask(mask, n: int, device: int):
-    """reset_envs' mask as n bytes on the device (a torch CUDA tensor is used in place)."""
+def _device_mask(mask, n: int, device: int, stream=None):
+    """reset_envs' mask as n bytes on the device (a uint8 torch CUDA tensor is used in place).
+    The upload and the conversion of any other mask are queued on `stream`, the stream the
+    reset reads the bytes on (None: torch's current stream, as the reset's null stream)."""
+    import contextlib
+
     import torch
     dev = torch.device("cuda", device)
     m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.asarray(mask))
     if m.numel() != n:
         raise ValueError(f"mask must have n_envs = {n} entries, got {m.numel()}")
-    m = m.reshape(-1).to(device=dev)
-    return (m != 0).to(torch.uint8).contiguous() if m.dtype != torch.uint8 else m.contiguous()
+    if isinstance(stream, torch.cuda.Stream):
+        on = torch.cuda.stream(stream)
+    elif _stream_handle(stream):
+        on = torch.cuda.stream(torch.cuda.ExternalStream(_stream_handle(stream), device=dev))
+    else:
+        on = contextlib.nullcontext()
+    with on:
+        m = m.reshape(-1).to(device=dev)
+        return (m != 0).to(torch.uint8).contiguous() if m.dtype != torch.uint8 else m.contiguous()
 
 
 def _ptr(a):
@@ -350,9 +361,13 @@ class Engine:
 
     def reset_envs(self, mask, stream=None):
         """reset(env_mask): re-place only the envs with a nonzero mask entry (n_envs entries:
-        a torch CUDA tensor on the engine's device is read in place, anything else is
-        uploaded).  See ffm_engine_reset_envs."""
-        m = _device_mask(mask, self.n_envs, self.device)
+        a uint8 torch CUDA tensor on the engine's device is read in place, anything else is
+        uploaded and converted).  The mask is read on `stream`, upload and conversion included:
+        a device mask must be ready on that stream.  Trajectory capture: a masked env keeps its
+        episode index k and its rows restart at step 1 (an env that had emptied logs again), so
+        drain_trajectories() before the call -- the drain sorts by (env, k, step) and would
+        interleave the two segments of one (env, k).  See ffm_engine_reset_envs."""
+        m = _device_mask(mask, self.n_envs, self.device, stream)
         _check(self._L.ffm_engine_reset_envs(self._h, C.c_void_p(m.data_ptr()), _stream_handle(stream)))
         self._mask_keep = m      # alive until the next call: the launch reads it asynchronously
 
@@ -787,8 +802,12 @@ class Learner:
         _check(self._L.ffm_learner_reset(self._h, _stream_handle(stream)))
 
     def reset_envs(self, mask, stream=None):
-        """reset(env_mask) of the batched learner: the masked envs only (ffm_learner_reset_envs)."""
-        m = _device_mask(mask, self.n_envs, self.device)
+        """reset(env_mask) of the batched learner: the masked envs only (ffm_learner_reset_envs).
+        The mask is read on `stream`, upload and conversion included (Engine.reset_envs).  A
+        masked env's position row holds its new placement and 0xFFFF behind it.  Trajectory
+        capture: a masked env keeps its episode index k and its rows restart at step 1, so
+        drain_trajectories() before the call (the drain sorts by (env, k, step))."""
+        m = _device_mask(mask, self.n_envs, self.device, stream)
         _check(self._L.ffm_learner_reset_envs(self._h, C.c_void_p(m.data_ptr()), _stream_handle(stream)))
         self._mask_keep = m
 

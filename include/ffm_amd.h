@@ -122,7 +122,12 @@ int ffm_engine_reset(ffm_engine* eng, void* stream);
  * engine's device, read on `stream`.  Philox only: the masked envs get the placement
  * ffm_engine_reset would give them (keyed by the step counter, which then advances), a zero
  * DFF and count n_agents; the other envs are untouched.  Episode counters are not changed
- * (an abandoned episode is not a completed one).  MT mode: FFM_E_UNSUPPORTED. */
+ * (an abandoned episode is not a completed one).  `mask` is read on `stream` and nowhere
+ * else: whatever produces the bytes -- an upload, a conversion from another type -- must be
+ * queued on `stream` before the call or be complete (the Python binding queues both there).
+ * Trajectory capture: a masked env keeps its k and its rows restart at step 1 (see
+ * ffm_engine_set_trajectory_capture); drain before the call.  With capture off the call
+ * launches the placement only.  MT mode: FFM_E_UNSUPPORTED. */
 int ffm_engine_reset_envs(ffm_engine* eng, const uint8_t* mask, void* stream);
 
 /* Advance every env by n_steps steps (model/ffm_core.py:36-104 each).  With n_steps > 1 a
@@ -165,6 +170,15 @@ int ffm_engine_get_mt_state(ffm_engine* eng, int64_t env, uint32_t* np_key, int3
  * (1-based), count} and the agent_capacity cells (x*W+y, live agents first in the
  * reference's order, 0xFFFF after); an episode's last row is the empty one of the step
  * that emptied the room.  An env that is already empty (auto_reset off) logs nothing.
+ * The rule, per step and selected env e: one row iff its k at the start of the step passes
+ * the period test, and none if e was empty before the step and is still empty after it.  The
+ * row's step is the number of steps since the latest of e's current placement (by
+ * ffm_engine_reset, ffm_engine_reset_envs or the auto-reset) and this call; count and cells
+ * are e's state after the step, and a step that ended the episode gives the empty row (the
+ * state before the re-placement).  ffm_engine_reset_envs changes no k: a masked env's rows
+ * go on under the same k from step 1 again, and one that had emptied logs again (what the
+ * learner's capture does as well).  The drain's consumers sort by (env, k, step), which
+ * would interleave the two segments of one (env, k): drain before a masked reset.
  * Rows past capacity_rows are dropped and counted.  While capture is on, ffm_engine_step
  * makes one launch per step (fused steps are off).  n_sel = 0 turns capture off. */
 int ffm_engine_set_trajectory_capture(ffm_engine* eng, const int32_t* envs, const int32_t* phases, int32_t n_sel,
@@ -332,9 +346,12 @@ int ffm_learner_reset(ffm_learner* l, void* stream);
  * per-episode reset, run_unified_actor_training.py:263): the envs whose byte in the DEVICE
  * array `mask` (n_envs bytes) is nonzero are re-placed as ffm_learner_reset places them
  * (Philox keyed by the step counter, which then advances; an env past its episode quota
- * stays empty), their DFF zeroed and their episode step count cleared.  Not an episode end:
- * nothing is logged or counted, and the tables are untouched.  Between steps only; MT mode:
- * FFM_E_UNSUPPORTED. */
+ * stays empty), their DFF zeroed and their episode step count cleared.  A masked env's
+ * position row holds the new placement and 0xFFFF in every slot behind it (an env past its
+ * quota: 0xFFFF only), as after ffm_learner_reset.  Not an episode end: nothing is logged or
+ * counted, and the tables are untouched.  `mask` is read on `stream` and nowhere else
+ * (ffm_engine_reset_envs).  Trajectory capture: a masked env keeps its k and its rows restart
+ * at step 1 -- drain before the call.  Between steps only; MT mode: FFM_E_UNSUPPORTED. */
 int ffm_learner_reset_envs(ffm_learner* l, const uint8_t* mask, void* stream);
 /* Asynchronous: returns once the steps are queued on `stream`.  A hashed V / H
  * table that passes 7/8 load drops the updates that would insert (the step goes
@@ -540,8 +557,11 @@ int ffm_learner_drain_episodes(ffm_learner* l, int32_t* records, int64_t cap, in
  * (k + phases[i]) % period == 0 (phases NULL: 0).  After every step of a captured episode one
  * row is appended: meta {global env, k, step in the episode (1-based), count} and the
  * agent_capacity cells (x*W+y, live agents first in the reference's order, 0xFFFF after),
- * i.e. the reference's `positions` after that step.  Rows past capacity_rows are dropped and
- * counted.  n_sel = 0 turns capture off.  Batched (Philox) learners only. */
+ * i.e. the reference's `positions` after that step.  The step counts from the env's current
+ * placement; ffm_learner_reset_envs changes no k, so a masked env's rows go on under the same
+ * k from step 1 again: drain before a masked reset (consumers sort by env, k, step).  Rows
+ * past capacity_rows are dropped and counted.  n_sel = 0 turns capture off.  Batched (Philox)
+ * learners only. */
 int ffm_learner_set_trajectory_capture(ffm_learner* l, const int32_t* envs, const int32_t* phases, int32_t n_sel,
                                        int32_t period, int64_t capacity_rows, void* stream);
 /* Rows captured since the last drain, in no particular order within a step (sort by
