@@ -57,8 +57,8 @@ struct GroupCarve {
 };
 
 // The staged positions are dead once the agents are marked, so the kept-prefix
-// array reuses them; the placement keys are used only after the step loop, so
-// they reuse the grids and tiles.
+// array reuses them; the placement keys are used only after the step loop (the
+// single-group form: after the step's stencil), so they reuse the grids and tiles.
 template <int G>
 __host__ __device__ inline GroupCarve group_carve(int PHW, int TS, int F) {
     GroupCarve c;
@@ -261,6 +261,10 @@ __device__ __forceinline__ uint32_t group_exact_coop(unsigned long long pend, ui
 #define FFM_GROUP_STAGGER 0
 #endif
 
+#ifndef FFM_GROUP_ONE_WAVES
+#define FFM_GROUP_ONE_WAVES 6   // the same for the single-group form (ONE)
+#endif
+
 #ifndef FFM_GROUP_WAVES
 #define FFM_GROUP_WAVES 6   // minimum waves per SIMD asked of the register allocator (G = 4 needs 73 VGPRs; the grid holds 6 per SIMD)
 #endif
@@ -282,8 +286,16 @@ constexpr int kGroupGSmall = FFM_GROUP_G_SMALL;   // envs per group when the lar
 
 // EPL: the episode log (episode_log.h) as a kernel of its own, as KD1 is (group_op): behind a
 // runtime pointer its code costs the step 4 VGPRs with the log off.
-template <int NB, int HT, int WT, int G, bool KD1, bool EPL>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FFM_GROUP_WAVES, 8)))
+// ONE: the single-group form, for grids whose every wave steps at most one group (4 * blocks >=
+// groups: every test-sized engine, every launch below the shard threshold at its default grid).
+// The step is the loop form's one iteration, phase for phase and draw for draw, without the loop:
+// the group's loads are issued at entry and nothing is prefetched (so no empty resource and no
+// second group state), a wave without a group skips the step under one wave-uniform guard (it
+// still meets the prologue's barrier), and the envs that emptied are re-placed straight from the
+// step's ballot, in ascending env order as the loop form's deferred mask gives them, once the DFF
+// is stored (no mask word in LDS).
+template <int NB, int HT, int WT, int G, bool KD1, bool EPL, bool ONE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ONE ? FFM_GROUP_ONE_WAVES : FFM_GROUP_WAVES, 8)))
 void core_group_kernel(CoreStepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int H = HT, W = WT, HW = H * W, PW = W + 2, PHW = (H + 2) * PW;
@@ -386,7 +398,7 @@ void core_group_kernel(CoreStepArgs a) {
     // defined (a `return` there cost 8-14 VGPRs)
     const __amdgpu_buffer_rsrc_t rZ = pair_rsrc(a.dff, 0);
     auto load = [&](int gg, GState& st) {
-        const bool ok = gg >= 0;
+        const bool ok = ONE || gg >= 0;   // ONE loads its own group only
         const int e0 = ok ? gg * G : 0;
         const __amdgpu_buffer_rsrc_t rc = ok ? rC : rZ, rp = ok ? rP : rZ, rd = ok ? rD : rZ;
         st.c = (int)__builtin_amdgcn_raw_buffer_load_b32(rc, lane < G ? lane * 4 : kOOB, e0 * 4, 0);
@@ -409,7 +421,8 @@ void core_group_kernel(CoreStepArgs a) {
         if (mine < most) __builtin_amdgcn_s_sleep(FFM_GROUP_STAGGER);
     }
     GState cur;
-    load(g < ngroups ? g : -1, cur);
+    if (!ONE) load(g < ngroups ? g : -1, cur);
+    else if (g < ngroups) load(g, cur);   // wave-uniform; cur is read under the same guard only
 
     if (LAD >= 1) {
     // Block-shared region: the image's first sq4 float4s, one 16-byte load and LDS store per
@@ -435,7 +448,7 @@ void core_group_kernel(CoreStepArgs a) {
     // group's loads return the arrays' zeroed padding, and loads past the last group go through
     // the empty resource and return zero.  Nothing ever writes the halo.
     if ((geo >> 24) != 255u) reinterpret_cast<float4*>(tile)[geo >> 24] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (lane < kGroupPendWords) pend[lane] = 0u;
+    if (!ONE && lane < kGroupPendWords) pend[lane] = 0u;
     // the block-shared region is first read by decide (the SFF term) and by the placement tail
     __syncthreads();
     }
@@ -462,6 +475,7 @@ void core_group_kernel(CoreStepArgs a) {
                 const int q = k * 64 + lane;
                 buf_st4(rq, q < Q ? q * 16 : kOOB, cur.d[k]);
             }
+            if (ONE) break;
             GState nx;
             load(g + wstride < ngroups ? g + wstride : -1, nx);
             cur = nx;
@@ -474,7 +488,7 @@ void core_group_kernel(CoreStepArgs a) {
 #pragma unroll
         for (int k = 0; k < NS; k++)
             if (k < NSF || toff[k] >= 0) *reinterpret_cast<float4*>(tile + toff[k]) = cur.d[k];
-        if (PF == 3) load(gn, nxt);
+        if (!ONE && PF == 3) load(gn, nxt);
         unsigned long long rsm = 0ull;   // envs re-placed at the end of this step
         if (LAD == 2) wave_sync();       // ladder rung 2: the staged tile before the stencil reads it
         if (LAD >= 3) {
@@ -516,7 +530,7 @@ void core_group_kernel(CoreStepArgs a) {
         }
         wave_sync();
 
-        if (PF == 2) load(gn, nxt);
+        if (!ONE && PF == 2) load(gn, nxt);
         // ---- decide (model/ffm_core.py:40-88) -------------------------------------------
 #pragma unroll
         for (int c = 0; c < MAXC; c++) {
@@ -564,7 +578,7 @@ void core_group_kernel(CoreStepArgs a) {
         }
         wave_sync();
 
-        if (PF == 1) load(gn, nxt);
+        if (!ONE && PF == 1) load(gn, nxt);
         // ---- resolve (model/ffm_core.py:90-98), by each requester ------------------------
         unsigned long long km[MAXC];
         int kept = 0;
@@ -658,7 +672,7 @@ void core_group_kernel(CoreStepArgs a) {
         if (rsm) {   // wave-uniform, rare
             c_resets += (unsigned)__popcll(rsm);
             if (a.episodes && rs) a.episodes[e0 + lane] += 1;
-            if (lane == 0) pend[iter >> 2] |= (uint32_t)rsm << (8 * (iter & 3));
+            if (!ONE && lane == 0) pend[iter >> 2] |= (uint32_t)rsm << (8 * (iter & 3));
         }
         // episode log (episode_log.h): with auto_reset every ended env is in rsm, so the
         // ballot of ending lanes is taken inside that rare branch only
@@ -668,7 +682,7 @@ void core_group_kernel(CoreStepArgs a) {
 
         // ---- next group's HBM loads, in flight across the stencil, the stores and the
         // next group's head ------------------------------------------------------------
-        if (PF == 0 || LAD < 3) load(gn, nxt);
+        if (!ONE && (PF == 0 || LAD < 3)) load(gn, nxt);
 
 #if FFM_GROUP_PROBE_VALU > 0 || FFM_GROUP_PROBE_SALU > 0
         {   // diagnostic issue probes (timing only): N extra VALU / SALU instructions per group
@@ -720,6 +734,15 @@ void core_group_kernel(CoreStepArgs a) {
                 b[dx + 1][0] = a.c0 * tile[NB == 4 ? lo[k] : yl ? 0 : tb + dx * W - 1];   // tile[0] == 0
                 b[dx + 1][5] = a.c0 * tile[NB == 4 ? ro[k] : yr ? 0 : tb + dx * W + 4];
             }
+            if (NB == 8 && ONE) {
+                // Moore, straight-line form: pin every B value to a register.  Without the loop
+                // around it the compiler packs the sums below by passing b[][] through private
+                // memory (80 bytes of scratch, re-read at shifted offsets).
+#pragma unroll
+                for (int r = 0; r < 3; r++)
+#pragma unroll
+                    for (int cc = 0; cc < 6; cc++) asm volatile("" : "+v"(b[r][cc]));
+            }
             float o[4];
 #pragma unroll
             for (int jj = 0; jj < 4; jj++) {
@@ -739,14 +762,28 @@ void core_group_kernel(CoreStepArgs a) {
                                                    rD, (k * 64 + lane) * 16, e0 * HW * 4, 0);
         }
         wave_sync();
+        if (ONE) {
+            // ---- auto-reset placements, from the step's own ballot: the grids
+            // and tiles the keys reuse are dead past the stencil's wave_sync above
+            static_assert((H - 2) * (W - 2) <= 128, "wave_reset_env<.., SMALL>");
+            uint32_t m = (uint32_t)rsm;   // wave-uniform, rarely non-zero
+            while (m) {
+                const long long e = (long long)e0 + __builtin_ctz(m);
+                m &= m - 1u;
+                wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane);
+                if (FFM_GROUP_ABLATE & 1)   // diagnostic: the same placement again (identical result)
+                    wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane);
+            }
+            break;
+        }
         cur = nxt;
     }
 
     // ---- deferred auto-reset placements ------------------------------
     // c_resets (wave-uniform) counts the bits set in pend: most waves re-place no env and skip
     // the tail with its setup (the placement's loop invariants)
-    if (c_resets) wave_sync();
-    for (int w = 0; w < (LAD >= 1 && c_resets ? kGroupPendWords : 0); w++) {   // ladder rung 0: pend never initialised
+    if (!ONE && c_resets) wave_sync();
+    for (int w = 0; w < (!ONE && LAD >= 1 && c_resets ? kGroupPendWords : 0); w++) {   // ladder rung 0: pend never initialised
         uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)pend[w]);
         while (m) {
             const int bit = w * 32 + __builtin_ctz(m);
@@ -821,11 +858,11 @@ void core_group_stage_build(int H, int W, int F, const uint8_t* pmap, const floa
 // KD1: k_D == 1 (the drivers' setting), where k_D * DFF is DFF itself: a kernel of its own
 // rather than a runtime flag, which the register allocator would keep (and spill) all launch.
 template <int NB, bool KD1, int G>
-static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int op, int* occ) {
+static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int op, int* occ, bool one) {
     const size_t smem = core_group_smem_bytes(a.H, a.W, a.F, 4, G);
     if (op) {
         *occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1, false>, 256, smem) !=
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1, false, false>, 256, smem) !=
             hipSuccess)
             *occ = 0;
         return hipSuccess;
@@ -836,27 +873,39 @@ static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int
     // the prologue copies the image's block-shared part with one 16-byte load per thread
     if (!a.stage || a.stage_q4 != core_group_stage_q4(a.H, a.W, a.F) || a.stage_q4 > 256)
         return hipErrorInvalidConfiguration;
-    if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
-    else core_group_kernel<NB, 12, 12, G, KD1, false><<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a);
+    // the single-group form wherever no wave of the grid steps a second group
+    const dim3 grid((unsigned)blocks), block(256);
+    if (one && core_group_one_group(a.E, blocks, G)) {
+        if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true, true><<<grid, block, smem, s>>>(a);
+        else core_group_kernel<NB, 12, 12, G, KD1, false, true><<<grid, block, smem, s>>>(a);
+    } else {
+        if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true, false><<<grid, block, smem, s>>>(a);
+        else core_group_kernel<NB, 12, 12, G, KD1, false, false><<<grid, block, smem, s>>>(a);
+    }
     return hipGetLastError();
 }
 
 template <int NB>
-static hipError_t group_op_kd(const CoreStepArgs& a, int blocks, hipStream_t s, int op, int* occ, int G) {
+static hipError_t group_op_kd(const CoreStepArgs& a, int blocks, hipStream_t s, int op, int* occ, int G, bool one) {
     if (G == kGroupGSmall)
-        return a.kD32 == 1.0f ? group_op<NB, true, kGroupGSmall>(a, blocks, s, op, occ)
-                              : group_op<NB, false, kGroupGSmall>(a, blocks, s, op, occ);
-    return a.kD32 == 1.0f ? group_op<NB, true, kGroupG>(a, blocks, s, op, occ)
-                          : group_op<NB, false, kGroupG>(a, blocks, s, op, occ);
+        return a.kD32 == 1.0f ? group_op<NB, true, kGroupGSmall>(a, blocks, s, op, occ, one)
+                              : group_op<NB, false, kGroupGSmall>(a, blocks, s, op, occ, one);
+    return a.kD32 == 1.0f ? group_op<NB, true, kGroupG>(a, blocks, s, op, occ, one)
+                          : group_op<NB, false, kGroupG>(a, blocks, s, op, occ, one);
 }
 
-hipError_t launch_core_group(const CoreStepArgs& a, int nb, int blocks, hipStream_t s, int G) {
-    return nb == 4 ? group_op_kd<4>(a, blocks, s, 0, nullptr, G) : group_op_kd<8>(a, blocks, s, 0, nullptr, G);
+// Whether a launch of E envs on `blocks` blocks has every wave step at most one group.
+bool core_group_one_group(long long E, int blocks, int G) { return 4ll * blocks >= (E + G - 1) / G; }
+
+// one: the single-group form where the grid allows it (core_group_one_group); false keeps the
+// loop form on every grid (FFM_GROUP_ONE=0).
+hipError_t launch_core_group(const CoreStepArgs& a, int nb, int blocks, hipStream_t s, int G, bool one) {
+    return nb == 4 ? group_op_kd<4>(a, blocks, s, 0, nullptr, G, one) : group_op_kd<8>(a, blocks, s, 0, nullptr, G, one);
 }
 
 int core_group_blocks_per_cu(const CoreStepArgs& a, int nb, int G) {
     int n = 0;
-    (void)(nb == 4 ? group_op_kd<4>(a, 0, nullptr, 1, &n, G) : group_op_kd<8>(a, 0, nullptr, 1, &n, G));
+    (void)(nb == 4 ? group_op_kd<4>(a, 0, nullptr, 1, &n, G, false) : group_op_kd<8>(a, 0, nullptr, 1, &n, G, false));
     return n;
 }
 

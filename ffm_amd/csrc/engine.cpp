@@ -55,6 +55,7 @@ struct ffm_engine {
     bool group = false;     // group kernel (lane conditions at 12x12): core_group.hip
     int group_blocks = 0;   // persistent grid of the group kernel
     int group_g = 4;        // envs per group (core_group_pick_envs)
+    bool group_one = true;  // the single-group form where a grid allows it (FFM_GROUP_ONE)
     bool multi = false;     // multi-step kernel available (lane conditions): core_multi.hip
     int multi_blocks = 0;   // its persistent grid
     int fused = 1;          // steps per launch (ffm_engine_set_fused_steps)
@@ -119,6 +120,9 @@ struct ffm_engine {
 static bool steps_group(const ffm_engine* e) { return e->group && !e->d_envp; }
 static bool steps_lane(const ffm_engine* e) { return e->d_envp ? e->pep_lane : e->lane; }
 static bool steps_wave(const ffm_engine* e) { return e->wave && !e->d_envp; }
+// Blocks per CU of the group kernel's largest grid (engine create, group_grid).
+constexpr int kGroupGridPerCu = 8;
+
 static int lane_blocks_now(const ffm_engine* e) { return e->d_envp ? e->pep_lane_blocks : e->lane_blocks; }
 
 // The lane kernel's persistent grid for n_envs envs (a.envp set: of its per-env form).
@@ -385,18 +389,25 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
             }
         }
         if (e->group) {
-            // at most 6 blocks (6 waves per SIMD) per CU: the group kernel fits 7 (71 VGPRs), but 7
-            // waves per SIMD step slower (65,536 envs 36.0 vs 33.0 us, 32,768 envs 23.1 vs 21.6 us),
-            // and fewer blocks than 6 per CU are slower too (1,366 blocks 36.5 us; 1,024 blocks at
-            // 32,768 envs 23.6 us): profiles/r06/c2/ab_grid_balance*.log, ab_occupancy7.log
+            // The loop form's resident blocks, at most 6 (6 waves per SIMD) per CU: what the shard
+            // rule and the group-size picker count with (as a one-launch grid, 7 per CU stepped
+            // slower and so did fewer than 6: profiles/r06/c2/ab_grid_balance*.log,
+            // ab_occupancy7.log).
             auto resident_cap = [&](int G) {
                 const int per_cu = std::max(1, ffm::core_group_blocks_per_cu(a, d.neighborhood, G));
                 return (long long)cus * std::min(per_cu, 6);
             };
-            // the persistent grid of a launch of n envs
+            // FFM_GROUP_ONE=0|1 (A/B and test switch, read at create): 0 keeps the loop form of
+            // the group kernel on every grid; unset or 1, a launch whose waves step at most one
+            // group each takes the single-group form (core_group.hip, ONE)
+            if (const char* ov = std::getenv("FFM_GROUP_ONE")) e->group_one = std::atoi(ov) != 0;
+            // The grid of a launch of n envs: a wave per group up to kGroupGridPerCu blocks per CU
+            // (2,048 on MI355X: each of the headline's two shards of 8,192 groups then takes the
+            // single-group form, whose 56 VGPRs and 22.4 KB of LDS keep 7 blocks per CU
+            // resident; profiles/one_group/), the persistent loop beyond.
             auto group_grid = [&](long long n, int G) {
                 const long long groups = (n + G - 1) / G;
-                long long b = std::max<long long>(1, std::min<long long>((groups + 3) / 4, resident_cap(G)));
+                long long b = std::max<long long>(1, std::min<long long>((groups + 3) / 4, (long long)cus * kGroupGridPerCu));
                 if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {   // diagnostic override of the grid
                     const long long v = std::atoll(ov);
                     if (v > 0) b = std::min<long long>(v, (groups + 3) / 4);
@@ -597,7 +608,7 @@ static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
             if (base.ep_start) a.ep_start = base.ep_start + sh.e0;   // records carry global ids through env_base
             a.counters = base.counters + 4 * sh.ctr0;
             a.no_step_count = k != 0;   // one shard per step counts the step
-            he = ffm::launch_core_group(a, e->d.neighborhood, sh.blocks, k ? e->sh_stream[k - 1] : s, sh.g);
+            he = ffm::launch_core_group(a, e->d.neighborhood, sh.blocks, k ? e->sh_stream[k - 1] : s, sh.g, e->group_one);
         }
     }
     // the join also after a failed launch: what was enqueued stays ordered before the caller's next work
@@ -639,7 +650,7 @@ int ffm_engine_step(ffm_engine* e, int32_t n_steps, void* stream) {
     }
     for (int i = 0; i < n_steps; i++) {
         ffm::CoreStepArgs a = make_args(e);
-        if (steps_group(e)) HIP_TRY(ffm::launch_core_group(a, e->d.neighborhood, e->group_blocks, s, e->group_g));
+        if (steps_group(e)) HIP_TRY(ffm::launch_core_group(a, e->d.neighborhood, e->group_blocks, s, e->group_g, e->group_one));
         else if (steps_lane(e)) HIP_TRY(ffm::launch_core_lane(a, e->d.neighborhood, lane_blocks_now(e), s));
         else if (steps_wave(e)) HIP_TRY(ffm::launch_core_wave(a, e->d.neighborhood, e->mt, e->wave_blocks, s));
         else HIP_TRY(ffm::launch_core_block(a, e->d.neighborhood, e->f64, e->mt, e->block, s));
@@ -1132,15 +1143,24 @@ int ffm_debug_reset_candidates(ffm_engine* e, int32_t* m, uint32_t* thr) {
 //   out[5] 1 if the fused multi-step kernel is available, out[6] its grid's blocks
 //   out[7] env shards a step(n > 1) call runs as under the current settings (1: one launch per
 //          step over all envs), out[8] blocks of one shard's grid (the first's; out[2] if one shard)
+//   out[9] the group kernel's form in the launches of such a call (its out[7] shards, or the one
+//          launch): 1 if every one of them takes the single-group form, 0 for the loop form (and
+//          for the other kernels)
 int ffm_debug_launch_info(ffm_engine* e, int32_t* out, int n) {
-    if (!e || !out || n < 0 || n > 9) return fail(FFM_E_INVALID, "bad args");
+    if (!e || !out || n < 0 || n > 10) return fail(FFM_E_INVALID, "bad args");
     const bool group = steps_group(e), lane = steps_lane(e), wave = steps_wave(e);
     const int kernel = group ? 0 : lane ? 1 : wave ? 2 : e->big ? 4 : 3;
     const long long E = e->d.n_envs;
     const int S = shards_in_effect(e);
     const int32_t step_blocks = group ? e->group_blocks : lane ? lane_blocks_now(e) : wave ? e->wave_blocks
                                                                                         : (int32_t)((E + e->K - 1) / e->K);
-    const int32_t v[9] = {
+    bool one = group && e->group_one;
+    if (one && S > 1) {
+        for (const ffm_engine::Shard& sh : e->shards) one = one && ffm::core_group_one_group(sh.n, sh.blocks, sh.g);
+    } else if (one) {
+        one = ffm::core_group_one_group(E, e->group_blocks, e->group_g);
+    }
+    const int32_t v[10] = {
         kernel,
         group ? e->group_g : 0,
         step_blocks,
@@ -1150,6 +1170,7 @@ int ffm_debug_launch_info(ffm_engine* e, int32_t* out, int n) {
         e->multi ? e->multi_blocks : 0,
         S,
         S > 1 ? e->shards[0].blocks : step_blocks,
+        one ? 1 : 0,
     };
     for (int i = 0; i < n; i++) out[i] = v[i];
     return FFM_OK;

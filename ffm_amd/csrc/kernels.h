@@ -116,7 +116,8 @@ int core_group_stage_q4(int H, int W, int F);
 void core_group_stage_build(int H, int W, int F, const uint8_t* pmap, const float* psff, float kS32,
                             const uint16_t* free_padded, unsigned char* out);
 int core_group_pick_envs(const CoreStepArgs& a, int nb, long long E, int cus);   // envs per group (2 or 4)
-hipError_t launch_core_group(const CoreStepArgs& a, int nb, int blocks, hipStream_t s, int G);
+hipError_t launch_core_group(const CoreStepArgs& a, int nb, int blocks, hipStream_t s, int G, bool one = true);
+bool core_group_one_group(long long E, int blocks, int G);   // every wave of the grid steps at most one group
 int core_group_blocks_per_cu(const CoreStepArgs& a, int nb, int G);
 size_t core_multi_smem_bytes(int H, int W, int F, int waves);
 hipError_t launch_core_multi(const CoreStepArgs& a, int nb, int nsteps, int blocks, hipStream_t s);

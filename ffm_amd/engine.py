@@ -641,12 +641,14 @@ class Engine:
         group (0 for the other kernels), the step grid's blocks, the block kernel's envs per
         workgroup K, the block size, the fused multi-step kernel's availability and grid, and the
         env shards a step(n > 1) call runs as under the current settings (1 = one launch per step
-        over all envs) with the blocks of one shard's grid."""
-        v = np.zeros(9, np.int32)
+        over all envs) with the blocks of one shard's grid, and whether those launches take the
+        group kernel's single-group form ("group_one"; False: its loop form, or another kernel)."""
+        v = np.zeros(10, np.int32)
         _check(self._L.ffm_debug_launch_info(self._h, _ptr(v), len(v)))
         return {"kernel": ("group", "lane", "wave", "block", "block_scratch")[int(v[0])], "group_g": int(v[1]),
                 "blocks": int(v[2]), "K": int(v[3]), "block_size": int(v[4]), "multi": bool(v[5]),
-                "multi_blocks": int(v[6]), "step_shards": int(v[7]), "shard_blocks": int(v[8])}
+                "multi_blocks": int(v[6]), "step_shards": int(v[7]), "shard_blocks": int(v[8]),
+                "group_one": bool(v[9])}
 
     def stage_image(self) -> np.ndarray:
         """The group kernel's engine-constant stage image as bytes (diagnostic,
