@@ -27,7 +27,8 @@
 //  * the order-preserving exit compaction (model/ffm_core.py:100-102) works on
 //    the packed order: the exclusive kept-prefix of every packed index goes to
 //    LDS, an agent's new index is its prefix minus the prefix at its env's
-//    start, an env's new count the difference of the prefixes at its bounds;
+//    start, an env's new count the difference of the prefixes at its bounds (the
+//    single-group form reads both from the lanes that hold them instead);
 //  * the owner's friction bit (the top bit of its Philox word z) rides in bit 12
 //    of its grid code, so the shared friction words are one dword per agent.
 #include <hip/hip_runtime.h>
@@ -59,7 +60,10 @@ struct GroupCarve {
 // The staged positions are dead once the agents are marked, so the kept-prefix
 // array reuses them; the placement keys are used only after the step loop (the
 // single-group form: after the step's stencil), so they reuse the grids and tiles.
-template <int G>
+// FIT: the single-group form's own carve (kGroupFitCarve, an A/B build): grids, tiles, friction
+// words and the dummy word only.  That build takes the staged positions and the kept prefixes
+// from the lanes' registers, and the form never defers a placement.
+template <int G, bool FIT = false>
 __host__ __device__ inline GroupCarve group_carve(int PHW, int TS, int F) {
     GroupCarve c;
     size_t o = 0;
@@ -70,6 +74,12 @@ __host__ __device__ inline GroupCarve group_carve(int PHW, int TS, int F) {
     if (o < keys_end) o = keys_end;
     c.words = o; o += (size_t)G * 32 * 4;
     c.posst = o;
+    if (FIT) {
+        c.kp = c.pend = o;   // none of the three exists in this carve
+        c.dummy = o; o += 4;
+        c.per_wave = a16(o);
+        return c;
+    }
     // the compaction writes an entry for every lane of every agent chunk (idle lanes too: no
     // exec-mask branch), so the array spans whole chunks: (G * 32 + 63) / 64 * 64 + 1 entries
     c.kp = o;    o += a16((size_t)(((G * 32 + 63) / 64) * 64 + 1) * 2);
@@ -84,6 +94,10 @@ __host__ __device__ inline GroupCarve group_carve(int PHW, int TS, int F) {
 __host__ __device__ inline size_t group_shared_bytes(int PHW, int F) {
     return a16((size_t)PHW) + a16((size_t)PHW * 4) + a16((size_t)(F > 0 ? F : 1) * 2) + a16((size_t)PHW * 2);
 }
+// The single-group form's block-shared region under kGroupFitCarve: the SFF term alone.  The map and
+// the widened map are never read from LDS, and the free list, which only a placement reads, stays
+// in the image in global memory.
+__host__ __device__ inline size_t group_one_shared_bytes(int PHW) { return a16((size_t)PHW * 4); }
 
 // The stage image (CoreStepArgs::stage): the block-shared region above byte for byte (pads zero),
 // then one table per group size of the per-lane slot geometry, which depends on (G, lane) only.
@@ -261,8 +275,22 @@ __device__ __forceinline__ uint32_t group_exact_coop(unsigned long long pend, ui
 #define FFM_GROUP_STAGGER 0
 #endif
 
+// The single-group form's LDS turns and arrays (profiles/lds_fit/).  1 is the product build; 0
+// (the form as it was), 2 and 3 are A/B builds: 2 and 3 measured slower at 32,768 envs.
+//   1: the compaction reads the kept prefixes from the lanes that hold them (no kp array)
+//   2: + the mark reads the positions from the lanes' registers (no posst array)
+//   3: + the form's own carve, 20,432 B per block at G = 4: eight blocks per CU
+#ifndef FFM_GROUP_FIT
+#define FFM_GROUP_FIT 1
+#endif
+constexpr bool kGroupFitCarve = FFM_GROUP_FIT >= 3;
+
 #ifndef FFM_GROUP_ONE_WAVES
-#define FFM_GROUP_ONE_WAVES 6   // the same for the single-group form (ONE)
+// The same for the single-group form (ONE).  Every instantiation stays below the 64 VGPRs of
+// eight waves per SIMD at 6 (tools/kernel_resources.py).  Asking for (8, 8) also cuts the SGPR
+// budget: FFM_GROUP_FIT=3 built that way spilled 10 - 99 scalars to VGPR lanes (SQ_INSTS_VALU
+// 671 -> 690 per wave in the headline kernel, profiles/lds_fit/).
+#define FFM_GROUP_ONE_WAVES 6
 #endif
 
 #ifndef FFM_GROUP_WAVES
@@ -312,16 +340,24 @@ void core_group_kernel(CoreStepArgs a) {
     constexpr int PWORDS = G * 16;             // position dwords per group (A <= 32)
     static_assert(G >= 1 && G <= 8 && HW % 4 == 0 && H + 1 < 128, "group geometry");
     static_assert(MAXC * 64 >= G * 32 && PWORDS * 4 <= (MAXC * 64 + 1) * 2, "kp spans the chunks; posst fits in it");
+    // what the single-group form does without, by FFM_GROUP_FIT
+    constexpr bool NOKP = ONE && FFM_GROUP_FIT >= 1, NOPOS = ONE && FFM_GROUP_FIT >= 2, FITC = ONE && kGroupFitCarve;
+    static_assert(!NOPOS || PWORDS <= 64, "the group's positions are one dword per lane");
+    static_assert(!NOKP || MAXC <= 2, "the kept prefixes are read from the first or the last chunk");
     const int A = a.A;
     const int lane = (int)(threadIdx.x & 63);
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 
-    const GroupCarve cv = group_carve<G>(PHW, TS, a.F);
+    const GroupCarve cv = group_carve<G, FITC>(PHW, TS, a.F);
     // block-shared (group_shared_bytes): the map and the widened map are in the image too, but
-    // the kernel reads only the SFF term and the free list from LDS
-    const float* psff = reinterpret_cast<const float*>(smem + a16((size_t)PHW));
-    const uint16_t* pfree = reinterpret_cast<const uint16_t*>(smem + a16((size_t)PHW) + a16((size_t)PHW * 4));
-    unsigned char* wbase = smem + group_shared_bytes(PHW, a.F) + (size_t)wv * cv.per_wave;
+    // the kernel reads only the SFF term and the free list from LDS.  FITC: the SFF term alone
+    // (group_one_shared_bytes), and the free list is read where it lies in the image.
+    constexpr size_t kImgSff = ((size_t)PHW + 15) / 16 * 16, kImgFree = kImgSff + ((size_t)PHW * 4 + 15) / 16 * 16;
+    const float* psff = reinterpret_cast<const float*>(smem + (FITC ? 0 : kImgSff));
+    const uint16_t* pfree = FITC ? reinterpret_cast<const uint16_t*>(static_cast<const unsigned char*>(a.stage) + kImgFree)
+                                 : reinterpret_cast<const uint16_t*>(smem + kImgFree);
+    unsigned char* wbase = smem + (FITC ? group_one_shared_bytes(PHW) : group_shared_bytes(PHW, a.F)) +
+                           (size_t)wv * cv.per_wave;
     uint16_t* const grid = reinterpret_cast<uint16_t*>(wbase + cv.grid);
     float* const tile = reinterpret_cast<float*>(wbase + cv.tile);
     uint32_t* const words = reinterpret_cast<uint32_t*>(wbase + cv.words);
@@ -428,7 +464,13 @@ void core_group_kernel(CoreStepArgs a) {
     // Block-shared region: the image's first sq4 float4s, one 16-byte load and LDS store per
     // thread (the host checks sq4 <= 256).  The map, f32(-k_S) * SFF, the free list and the
     // widened map are engine constants: nothing is recomputed per launch.
-    if ((int)threadIdx.x < sq4)
+    // FITC: only the SFF term, PHW * 4 bytes of the image from kImgSff on.
+    static_assert((PHW * 4) % 16 == 0 && PHW * 4 / 16 <= 256, "16-B copies of the SFF term, one per thread");
+    if (FITC) {
+        if ((int)threadIdx.x < PHW * 4 / 16)
+            reinterpret_cast<uint4*>(smem)[threadIdx.x] = __builtin_bit_cast(
+                uint4, __builtin_amdgcn_raw_buffer_load_b128(rS, (int)threadIdx.x * 16, (int)kImgSff, 0));
+    } else if ((int)threadIdx.x < sq4)
         reinterpret_cast<uint4*>(smem)[threadIdx.x] = __builtin_bit_cast(
             uint4, __builtin_amdgcn_raw_buffer_load_b128(rS, (int)threadIdx.x * 16, 0, 0));
     // Every env's grid starts as the map: the widened map straight from the image (8 bytes per
@@ -492,15 +534,19 @@ void core_group_kernel(CoreStepArgs a) {
         unsigned long long rsm = 0ull;   // envs re-placed at the end of this step
         if (LAD == 2) wave_sync();       // ladder rung 2: the staged tile before the stencil reads it
         if (LAD >= 3) {
-        if (lane < PWORDS) posst32[lane] = cur.p0;
-        if (PWORDS > 64 && 64 + lane < PWORDS) posst32[64 + lane] = cur.p1;
+        // NOPOS: the positions stay in p0 of lanes 0..PWORDS-1; the mark reads them across lanes
+        if (!NOPOS && lane < PWORDS) posst32[lane] = cur.p0;
+        if (!NOPOS && PWORDS > 64 && 64 + lane < PWORDS) posst32[64 + lane] = cur.p1;
         int S[G + 1];   // exclusive prefix of the counts (wave-uniform)
         S[0] = 0;
 #pragma unroll
         for (int s = 0; s < G; s++) S[s + 1] = S[s] + __builtin_amdgcn_readlane(cur.c, s);
         const int T = S[G];
         c_steps += (unsigned)T;
-        wave_sync();
+        // posst before the mark reads it.  NOPOS: nothing in LDS to order here; the grids were
+        // initialised behind the prologue's barrier, and the staged tile is first read by decide,
+        // behind the mark's wave_sync
+        if (!NOPOS) wave_sync();
 
         // ---- packed agents: cell and occupancy mark ------------------------------------
         uint32_t cs[MAXC], cr[MAXC];
@@ -519,7 +565,15 @@ void core_group_kernel(CoreStepArgs a) {
                 }
                 const bool live = j < T;
                 const int al = live ? j - st : 0;
-                const uint32_t p = posst[live ? s * A + al : 0];
+                // NOPOS: half idx & 1 of position dword idx >> 1, held by that lane (idx < G * A <=
+                // 128); all lanes are active here (T is wave-uniform), as the permute needs
+                const int idx = live ? s * A + al : 0;
+                uint32_t p;
+                if (NOPOS) {
+                    const uint32_t pw = (uint32_t)__builtin_amdgcn_ds_bpermute((idx >> 1) * 4, (int)cur.p0);
+                    p = (idx & 1) ? pw >> 16 : pw & 0xFFFFu;
+                } else
+                    p = posst[idx];
                 const int x = (int)__umulhi(p, mW);
                 const int y = (int)p - x * W;
                 const int pp = live ? (x + 1) * PW + y + 1 : PW + 1;
@@ -639,13 +693,30 @@ void core_group_kernel(CoreStepArgs a) {
         for (int c = 0; c < MAXC; c++) {
             if (c * 64 < T) {
                 const uint32_t v = cs[c];
-                kp[c * 64 + lane] = (uint16_t)(cr[c] >> 17);   // idle lanes' entries are never read
+                if (!NOKP) kp[c * 64 + lane] = (uint16_t)(cr[c] >> 17);   // idle lanes' entries are never read
                 grid[cs_live(v) ? cs_s(v) * PHW + cs_pp(v) : kDummy16] = 0;   // unmark: agents stand on free cells
             }
         }
-        if (lane == 0) kp[T] = (uint16_t)kept;
+        if (!NOKP && lane == 0) kp[T] = (uint16_t)kept;
         c_exits += (unsigned)(T - kept);
-        wave_sync();
+        // NOKP: the kept prefix at an env's start is the popcount of the resolve ballots below it
+        // (the bits of idle lanes and of a chunk that did not run are zero, so base[G] = kept):
+        // wave-uniform, and no LDS turn before the position stores
+        int base[G + 1];
+        base[0] = 0;
+        base[G] = kept;
+#pragma unroll
+        for (int s = 1; s < G; s++) {
+            base[s] = 0;
+            if (NOKP) {
+                // the lane at packed index S[s] holds that popcount as its own kept prefix (a live
+                // lane of a chunk that ran, whenever S[s] < T; past T every later env is empty)
+                int b = __builtin_amdgcn_readlane((int)(cr[0] >> 17), S[s] & 63);
+                if (MAXC > 1) b = S[s] < 64 ? b : __builtin_amdgcn_readlane((int)(cr[MAXC - 1] >> 17), S[s] & 63);
+                base[s] = S[s] < T ? b : kept;
+            }
+        }
+        if (!NOKP) wave_sync();
 #pragma unroll
         for (int c = 0; c < MAXC; c++) {
             if (c * 64 < T) {
@@ -654,18 +725,30 @@ void core_group_kernel(CoreStepArgs a) {
                 const int s = cs_s(v);
                 const bool keep = ((w >> 16) & 1u) != 0u;
                 const int start = j - cs_al(v);
-                const int newidx = (int)(w >> 17) - (int)kp[cs_live(v) ? start : 0];
+                int bs = base[0];
+#pragma unroll
+                for (int q = 1; q < G; q++) bs = s == q ? base[q] : bs;
+                const int newidx = (int)(w >> 17) - (NOKP ? bs : (int)kp[cs_live(v) ? start : 0]);
                 __builtin_amdgcn_raw_buffer_store_b16((uint16_t)unpad((int)(w & 0xFFFFu), PW), rP,
                                                       keep ? (s * A + newidx) * 2 : kOOB, e0 * A * 2, 0);
             }
         }
         int Sl = T, Sh = T;   // lane s < G: [S[s], S[s+1])
+        int nk = 0;           // lane s < G: the env's new count
+        bool had;             // ... and whether it had agents
+        if (NOKP) {
 #pragma unroll
-        for (int s = 0; s < G; s++) {
-            Sl = lane == s ? S[s] : Sl;
-            Sh = lane == s ? S[s + 1] : Sh;
+            for (int s = 0; s < G; s++) nk = lane == s ? base[s + 1] - base[s] : nk;
+            had = cur.c > 0;
+        } else {
+#pragma unroll
+            for (int s = 0; s < G; s++) {
+                Sl = lane == s ? S[s] : Sl;
+                Sh = lane == s ? S[s + 1] : Sh;
+            }
+            nk = (int)kp[Sh] - (int)kp[Sl];
+            had = Sh > Sl;
         }
-        const int nk = (int)kp[Sh] - (int)kp[Sl];
         const bool rs = a.auto_reset && lane < nenv && nk == 0;
         rsm = __ballot(rs);
         __builtin_amdgcn_raw_buffer_store_b32((unsigned)(rs ? a.N : nk), rC, lane < G ? lane * 4 : kOOB, e0 * 4, 0);
@@ -677,7 +760,10 @@ void core_group_kernel(CoreStepArgs a) {
         // episode log (episode_log.h): with auto_reset every ended env is in rsm, so the
         // ballot of ending lanes is taken inside that rare branch only
         if (EPL && (rsm || !a.auto_reset))
-            eplog_end_wave(a, lane < nenv && nk == 0 && Sh > Sl, rs, e0 + lane, a.t, lane);
+            eplog_end_wave(a, lane < nenv && nk == 0 && had, rs, e0 + lane, a.t, lane);
+        // NOKP: the wave_sync that stood before the position stores also ordered resolve's adds to
+        // the tile (other lanes' LDS atomics) before the stencil's reads, so it stands here now
+        if (NOKP) wave_sync();
         }   // LAD >= 3
 
         // ---- next group's HBM loads, in flight across the stencil, the stores and the
@@ -806,10 +892,16 @@ void core_group_kernel(CoreStepArgs a) {
     }
 }
 
-size_t core_group_smem_bytes(int H, int W, int F, int waves, int G) {
-    const int PHW = (H + 2) * (W + 2);
-    const size_t per_wave = G == kGroupGSmall ? group_carve<kGroupGSmall>(PHW, lane_tile_floats(H, W), F).per_wave
-                                              : group_carve<kGroupG>(PHW, lane_tile_floats(H, W), F).per_wave;
+// one: the single-group form's own size (its carve and block-shared region, kGroupFitCarve).
+size_t core_group_smem_bytes(int H, int W, int F, int waves, int G, bool one) {
+    const int PHW = (H + 2) * (W + 2), TS = lane_tile_floats(H, W);
+    if (one && kGroupFitCarve) {
+        const size_t per_wave = G == kGroupGSmall ? group_carve<kGroupGSmall, true>(PHW, TS, F).per_wave
+                                                  : group_carve<kGroupG, true>(PHW, TS, F).per_wave;
+        return group_one_shared_bytes(PHW) + (size_t)waves * per_wave;
+    }
+    const size_t per_wave = G == kGroupGSmall ? group_carve<kGroupGSmall>(PHW, TS, F).per_wave
+                                              : group_carve<kGroupG>(PHW, TS, F).per_wave;
     return group_shared_bytes(PHW, F) + (size_t)waves * per_wave;
 }
 
@@ -859,12 +951,14 @@ void core_group_stage_build(int H, int W, int F, const uint8_t* pmap, const floa
 // rather than a runtime flag, which the register allocator would keep (and spill) all launch.
 template <int NB, bool KD1, int G>
 static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int op, int* occ, bool one) {
-    const size_t smem = core_group_smem_bytes(a.H, a.W, a.F, 4, G);
-    if (op) {
+    // each form at its own LDS size
+    const size_t smem = core_group_smem_bytes(a.H, a.W, a.F, 4, G), smem1 = core_group_smem_bytes(a.H, a.W, a.F, 4, G, true);
+    if (op) {   // the resident blocks per CU of the form `one` names
         *occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1, false, false>, 256, smem) !=
-            hipSuccess)
-            *occ = 0;
+        const hipError_t r =
+            one ? hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1, false, true>, 256, smem1)
+                : hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1, false, false>, 256, smem);
+        if (r != hipSuccess) *occ = 0;
         return hipSuccess;
     }
     const long long groups = (a.E + G - 1) / G;
@@ -876,8 +970,8 @@ static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int
     // the single-group form wherever no wave of the grid steps a second group
     const dim3 grid((unsigned)blocks), block(256);
     if (one && core_group_one_group(a.E, blocks, G)) {
-        if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true, true><<<grid, block, smem, s>>>(a);
-        else core_group_kernel<NB, 12, 12, G, KD1, false, true><<<grid, block, smem, s>>>(a);
+        if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true, true><<<grid, block, smem1, s>>>(a);
+        else core_group_kernel<NB, 12, 12, G, KD1, false, true><<<grid, block, smem1, s>>>(a);
     } else {
         if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true, false><<<grid, block, smem, s>>>(a);
         else core_group_kernel<NB, 12, 12, G, KD1, false, false><<<grid, block, smem, s>>>(a);
@@ -903,9 +997,10 @@ hipError_t launch_core_group(const CoreStepArgs& a, int nb, int blocks, hipStrea
     return nb == 4 ? group_op_kd<4>(a, blocks, s, 0, nullptr, G, one) : group_op_kd<8>(a, blocks, s, 0, nullptr, G, one);
 }
 
-int core_group_blocks_per_cu(const CoreStepArgs& a, int nb, int G) {
+// one: of the single-group form (diagnostic); the grid rules count with the loop form's.
+int core_group_blocks_per_cu(const CoreStepArgs& a, int nb, int G, bool one) {
     int n = 0;
-    (void)(nb == 4 ? group_op_kd<4>(a, 0, nullptr, 1, &n, G, false) : group_op_kd<8>(a, 0, nullptr, 1, &n, G, false));
+    (void)(nb == 4 ? group_op_kd<4>(a, 0, nullptr, 1, &n, G, one) : group_op_kd<8>(a, 0, nullptr, 1, &n, G, one));
     return n;
 }
 

@@ -1125,6 +1125,20 @@ int ffm_debug_stage_image(ffm_engine* e, void* out, int64_t cap, int64_t* n) {
     return FFM_OK;
 }
 
+// Diagnostic (not part of the ABI header): the blocks per CU the runtime reports resident
+// (hipOccupancyMaxActiveBlocksPerMultiprocessor) for this engine's group kernel -- its
+// neighbourhood, k_D and envs per group, the log-free instantiation -- in the single-group form
+// (one != 0) or the loop form, each at its own shared-memory size.  0 for the other kernels.
+int ffm_debug_group_occupancy(ffm_engine* e, int32_t one, int32_t* blocks_per_cu) {
+    if (!e || !blocks_per_cu) return fail(FFM_E_INVALID, "bad args");
+    *blocks_per_cu = 0;
+    if (!e->group) return FFM_OK;
+    HIP_TRY(hipSetDevice(e->d.device));
+    const ffm::CoreStepArgs a = make_args(e);
+    *blocks_per_cu = ffm::core_group_blocks_per_cu(a, e->d.neighborhood, e->group_g, one != 0);
+    return FFM_OK;
+}
+
 // Diagnostic: the placement's candidate count M and key threshold in effect (fixed at create).
 int ffm_debug_reset_candidates(ffm_engine* e, int32_t* m, uint32_t* thr) {
     if (!e || !m || !thr) return fail(FFM_E_INVALID, "bad args");

@@ -105,7 +105,7 @@ size_t core_lane_smem_bytes(int H, int W, int F, int waves);
 hipError_t launch_core_lane(const CoreStepArgs& a, int nb, int blocks, hipStream_t s);
 int core_lane_blocks_per_cu(const CoreStepArgs& a, int nb);
 int core_lane_max_pairs_per_wave();
-size_t core_group_smem_bytes(int H, int W, int F, int waves, int G = 4);
+size_t core_group_smem_bytes(int H, int W, int F, int waves, int G = 4, bool one = false);   // one: the single-group form's
 bool core_group_supported(int H, int W);
 int core_group_max_iters();
 // The stage image of the group kernel (CoreStepArgs::stage): its size, the float4s of its
@@ -118,7 +118,7 @@ void core_group_stage_build(int H, int W, int F, const uint8_t* pmap, const floa
 int core_group_pick_envs(const CoreStepArgs& a, int nb, long long E, int cus);   // envs per group (2 or 4)
 hipError_t launch_core_group(const CoreStepArgs& a, int nb, int blocks, hipStream_t s, int G, bool one = true);
 bool core_group_one_group(long long E, int blocks, int G);   // every wave of the grid steps at most one group
-int core_group_blocks_per_cu(const CoreStepArgs& a, int nb, int G);
+int core_group_blocks_per_cu(const CoreStepArgs& a, int nb, int G, bool one = false);   // one: of the single-group form
 size_t core_multi_smem_bytes(int H, int W, int F, int waves);
 hipError_t launch_core_multi(const CoreStepArgs& a, int nb, int nsteps, int blocks, hipStream_t s);
 int core_multi_blocks_per_cu(const CoreStepArgs& a, int nb);

@@ -650,6 +650,18 @@ class Engine:
                 "multi_blocks": int(v[6]), "step_shards": int(v[7]), "shard_blocks": int(v[8]),
                 "group_one": bool(v[9])}
 
+    def group_occupancy(self, one: bool = True) -> int:
+        """Blocks per CU the runtime reports resident for this engine's group kernel (diagnostic,
+        ffm_debug_group_occupancy): its single-group form (`one`) or its loop form, each at its
+        own shared-memory size; 0 for engines of the other kernels."""
+        # bound here, not in load_library(): a diagnostic outside the ABI header, and an A/B run's
+        # older library (FFM_LIB_PATH) must still load
+        fn = self._L.ffm_debug_group_occupancy
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)], C.c_int
+        n = C.c_int32()
+        _check(fn(self._h, 1 if one else 0, C.byref(n)))
+        return int(n.value)
+
     def stage_image(self) -> np.ndarray:
         """The group kernel's engine-constant stage image as bytes (diagnostic,
         ffm_debug_stage_image); empty for engines of the other kernels."""
