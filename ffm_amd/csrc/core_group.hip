@@ -170,10 +170,13 @@ __device__ __forceinline__ float lane_f32(float x, int l) {
 // the f32 sum from -0 and the f64 cumsum are folded over the valid candidates in candidate
 // order from the lanes' values (wave-uniform operands, dependent adds).  Called in wave-uniform
 // control flow with all lanes active; csv is the chunk's cs word, wx / wy the decide draw.
-template <int W, int PHW, int TS>
+// PEP: psff is the raw SFF, and lane s < G of kSv / kDv holds env s's f32(-k_S) / f32(k_D); the
+// pending agent's env is wave-uniform here, so its two values are one readlane each.
+template <int W, int PHW, int TS, bool PEP = false>
 __device__ __forceinline__ uint32_t group_exact_coop(unsigned long long pend, uint32_t slot, uint32_t csv, uint32_t wx,
                                                      uint32_t wy, const uint16_t* grid, const float* psff,
-                                                     const float* tile, float kD, int lane) {
+                                                     const float* tile, float kD, int lane, float kSv = 0.0f,
+                                                     float kDv = 0.0f) {
     constexpr int NB = 4, PW = W + 2;
     while (pend) {
         const int L = __builtin_ctzll(pend);   // lowest pending lane first
@@ -191,8 +194,8 @@ __device__ __forceinline__ uint32_t group_exact_coop(unsigned long long pend, ui
         const uint32_t g = grid[s * PHW + cell];
         // the valid candidates as a wave-uniform mask: free or exit neighbours, and the stay
         const unsigned vm = ((unsigned)__ballot(g == 0u || g == 3u) & ((1u << NB) - 1u)) | (1u << NB);   // :52-60
-        const float sa = psff[cell];
-        const float sb = kD * tile[s * TS + pp + dd0 + doff];
+        const float sa = PEP ? lane_f32(kSv, s) * psff[cell] : psff[cell];
+        const float sb = (PEP ? lane_f32(kDv, s) : kD) * tile[s * TS + pp + dd0 + doff];
         const float sc = sa + sb;                                                      // :77
         float mx = -__builtin_inff();
 #pragma unroll
@@ -303,6 +306,13 @@ constexpr bool kGroupFitCarve = FFM_GROUP_FIT >= 3;
 #define FFM_GROUP_COOP_EXACT 1
 #endif
 
+// PEP builds: how a lane takes the value of its agent's (its DFF slot's) env from the lanes that
+// hold the group's records.  1: one ds_bpermute per value; 0: G readlanes into wave-uniform
+// values and G - 1 selects (A/B builds; profiles/env_params_group/resources.txt has both).
+#ifndef FFM_GROUP_PEP_BPERMUTE
+#define FFM_GROUP_PEP_BPERMUTE 1
+#endif
+
 #ifndef FFM_GROUP_G
 #define FFM_GROUP_G 4
 #endif
@@ -322,7 +332,11 @@ constexpr int kGroupGSmall = FFM_GROUP_G_SMALL;   // envs per group when the lar
 // still meets the prologue's barrier), and the envs that emptied are re-placed straight from the
 // step's ballot, in ascending env order as the loop form's deferred mask gives them, once the DFF
 // is stored (no mask word in LDS).
-template <int NB, int HT, int WT, int G, bool KD1, bool EPL, bool ONE>
+// PEP: with per-env parameters (a.envp, kernels.h).  Lane s < G holds env s's record, loaded with
+// the group's state; decide takes the agent's env's kS32 / kD32 on the raw SFF (a.stage is then the
+// image built with multiplier 1), the stencil the c0 / c1 of each slot's env, the count store and
+// the placements the env's N.  No KD1 variant: k_D * DFF with k_D == 1 is DFF exactly.
+template <int NB, int HT, int WT, int G, bool KD1, bool EPL, bool ONE, bool PEP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ONE ? FFM_GROUP_ONE_WAVES : FFM_GROUP_WAVES, 8)))
 void core_group_kernel(CoreStepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -339,6 +353,7 @@ void core_group_kernel(CoreStepArgs a) {
     constexpr int MAXC = (G * 32 + 63) / 64;   // agent chunks per group (A <= 32)
     constexpr int PWORDS = G * 16;             // position dwords per group (A <= 32)
     static_assert(G >= 1 && G <= 8 && HW % 4 == 0 && H + 1 < 128, "group geometry");
+    static_assert(!PEP || !KD1, "the per-env form multiplies by every env's own k_D");
     static_assert(MAXC * 64 >= G * 32 && PWORDS * 4 <= (MAXC * 64 + 1) * 2, "kp spans the chunks; posst fits in it");
     // what the single-group form does without, by FFM_GROUP_FIT
     constexpr bool NOKP = ONE && FFM_GROUP_FIT >= 1, NOPOS = ONE && FFM_GROUP_FIT >= 2, FITC = ONE && kGroupFitCarve;
@@ -420,6 +435,9 @@ void core_group_kernel(CoreStepArgs a) {
     const __amdgpu_buffer_rsrc_t rC = pair_rsrc(a.cnt, Epad * 4);
     const __amdgpu_buffer_rsrc_t rP = pair_rsrc(a.pos, Epad * A * 2 + 4);   // + the dword of slack
     const __amdgpu_buffer_rsrc_t rD = pair_rsrc(a.dff, Epad * HW * 4);
+    // PEP: the records are not padded; what a partial last group reads past them is zero
+    const __amdgpu_buffer_rsrc_t rE = pair_rsrc(PEP ? (const void*)a.envp : (const void*)a.dff,
+                                                PEP ? (int)E * (int)sizeof(EnvParams) : 0);
     const int ngroups = (int)((E + G - 1) / G);
     const int wstride = (int)gridDim.x * 4;
     int g = (int)blockIdx.x * 4 + wv;
@@ -428,11 +446,23 @@ void core_group_kernel(CoreStepArgs a) {
         float4 d[NS];
         uint32_t p0, p1;
         int c;
+        float4 pr;   // PEP, lane s < G: kS32, kD32, c0, c1 of env s
     };
     // past the last group (the loop's final prefetch) the loads go through empty resources:
     // every lane's access is out of range, no bytes move, and no value is conditionally
     // defined (a `return` there cost 8-14 VGPRs)
     const __amdgpu_buffer_rsrc_t rZ = pair_rsrc(a.dff, 0);
+    auto load_rec = [&](int gg, GState& st) {   // PEP: the group's records, {kS32, kD32, c0, c1} of env `lane`
+        constexpr int RB = (int)sizeof(EnvParams);
+        // past the last group every lane's offset is out of range (no second resource to select).
+        // The offset is formed here, per load (opaque): as a loop invariant it is held through every
+        // iteration of the loop form (its G = 2 build with the episode log then spills 4 VGPRs).
+        const bool ok = ONE || gg >= 0;
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        st.pr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rE, ok && ln < G ? ln * RB : kOOB,
+                                                                                 (ok ? gg * G : 0) * RB, 0));
+    };
     auto load = [&](int gg, GState& st) {
         const bool ok = ONE || gg >= 0;   // ONE loads its own group only
         const int e0 = ok ? gg * G : 0;
@@ -448,6 +478,24 @@ void core_group_kernel(CoreStepArgs a) {
             st.d[k] = __builtin_bit_cast(float4,
                                          __builtin_amdgcn_raw_buffer_load_b128(rd, q < Q ? q * 16 : kOOB, e0 * HW * 4, 0));
         }
+        if constexpr (PEP) load_rec(gg, st);
+    };
+    // PEP: the value lane s holds (s < G, per lane: an agent's env, a DFF slot's env)
+    auto env_val = [&](float v, int s) {
+        if (FFM_GROUP_PEP_BPERMUTE)
+            return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(s * 4, __builtin_bit_cast(int, v)));
+        float r = lane_f32(v, 0);
+#pragma unroll
+        for (int q = 1; q < G; q++) r = s == q ? lane_f32(v, q) : r;
+        return r;
+    };
+    // PEP: the placement of env e of this launch with its own N and threshold, read here: rare,
+    // nothing of the step is live
+    auto place = [&](long long e) {
+        if constexpr (PEP)
+            wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane, a.envp[e].N,
+                                     a.envp[e].reset_thr);
+        else wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane);
     };
     constexpr int LAD = FFM_GROUP_LADDER;
     constexpr int PF = FFM_GROUP_PF;
@@ -600,18 +648,26 @@ void core_group_kernel(CoreStepArgs a) {
                 const float* dk = tile + s * TS;
                 const int dd0 = 3 - 2 * cs_xp1(v);
                 bool to_exit = false;
-                uint32_t slot = lane_decide<NB, true, KD1>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32, pb.x, to_exit);
+                // PEP: the agent's env's k_S / k_D (idle lanes: env 0's), on the raw SFF
+                float kSe = a.kS32, kDe = a.kD32;
+                if constexpr (PEP) {
+                    kSe = env_val(cur.pr.x, s);
+                    kDe = env_val(cur.pr.y, s);
+                }
+                uint32_t slot = PEP ? lane_decide<NB, false, false>(pp, PW, gk, psff, dk, dd0, kSe, kDe, pb.x, to_exit)
+                                    : lane_decide<NB, true, KD1>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32, pb.x, to_exit);
                 slot = live ? slot : kNoReq;
                 // u near a cdf boundary: the exact NumPy arithmetic decides
                 if (NB == 4 && FFM_GROUP_COOP_EXACT) {
                     const unsigned long long pm = __ballot(slot == kPending);
                     if (pm)   // wave-uniform, rare
-                        slot = group_exact_coop<W, PHW, TS>(pm, slot, v, pb.x, pb.y, grid, psff, tile, a.kD32, lane);
+                        slot = PEP ? group_exact_coop<W, PHW, TS, true>(pm, slot, v, pb.x, pb.y, grid, psff, tile, 0.0f,
+                                                                        lane, cur.pr.x, cur.pr.y)
+                                   : group_exact_coop<W, PHW, TS>(pm, slot, v, pb.x, pb.y, grid, psff, tile, a.kD32, lane);
                 } else if (slot == kPending)
-                    slot = NB == 4 ? lane_decide_exact<NB, true>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32,
-                                                                 u53(pb.x, pb.y))
-                                   : lane_decide_exact_arr<NB, true>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32,
-                                                               u53(pb.x, pb.y));
+                    slot = NB == 4 ? lane_decide_exact<NB, !PEP>(pp, PW, gk, psff, dk, dd0, kSe, kDe, u53(pb.x, pb.y))
+                                   : lane_decide_exact_arr<NB, !PEP>(pp, PW, gk, psff, dk, dd0, kSe, kDe,
+                                                                     u53(pb.x, pb.y));
                 const uint32_t sd = slot <= (uint32_t)NB ? slot : DirCodes::kNoDir;
                 grid[live ? s * PHW + pp : kDummy16] =
                     (uint16_t)(DirCodes::kAgent | (uint32_t)al | (sd << 8) | ((pb.z >> 31) << 12));
@@ -751,8 +807,11 @@ void core_group_kernel(CoreStepArgs a) {
         }
         const bool rs = a.auto_reset && lane < nenv && nk == 0;
         rsm = __ballot(rs);
-        __builtin_amdgcn_raw_buffer_store_b32((unsigned)(rs ? a.N : nk), rC, lane < G ? lane * 4 : kOOB, e0 * 4, 0);
+        __builtin_amdgcn_raw_buffer_store_b32((unsigned)(rs ? a.N : nk), rC, lane < G && !(PEP && rs) ? lane * 4 : kOOB, e0 * 4, 0);
         if (rsm) {   // wave-uniform, rare
+            // PEP: an emptied env's count is its own N, read here and stored by the env's lane in
+            // place of the store above (nothing of the record is held for it through the step)
+            if (PEP && rs) a.cnt[e0 + lane] = a.envp[e0 + lane].N;
             c_resets += (unsigned)__popcll(rsm);
             if (a.episodes && rs) a.episodes[e0 + lane] += 1;
             if (!ONE && lane == 0) pend[iter >> 2] |= (uint32_t)rsm << (8 * (iter & 3));
@@ -794,12 +853,14 @@ void core_group_kernel(CoreStepArgs a) {
             const float m0 = p[0], mu = p[-W], md = p[W], pl = p[-1], pr = p[1];
             const float ml = (geo & (1u << 20)) ? 0.0f : pl, mr = (geo & (2u << 20)) ? 0.0f : pr;
             // B = c0 * D per operand, then A = B + sum c1 * B[nb] in neighbour order (:106-117)
-            const float b0 = a.c0 * m0, bu = a.c0 * mu, bd = a.c0 * md, bl = a.c0 * ml, br = a.c0 * mr;
+            // PEP: env ts's own c0 / c1, from the lane that holds its record
+            const float c0 = PEP ? lane_f32(cur.pr.z, ts) : a.c0, c1 = PEP ? lane_f32(cur.pr.w, ts) : a.c1;
+            const float b0 = c0 * m0, bu = c0 * mu, bd = c0 * md, bl = c0 * ml, br = c0 * mr;
             float acc = b0;
-            acc = acc + a.c1 * bu;
-            acc = acc + a.c1 * bd;
-            acc = acc + a.c1 * bl;
-            acc = acc + a.c1 * br;
+            acc = acc + c1 * bu;
+            acc = acc + c1 * bd;
+            acc = acc + c1 * bl;
+            acc = acc + c1 * br;
             float o = acc < 1e-4f ? 0.0f : acc;
             if (rsm && ((rsm >> ts) & 1ull)) o = 0.0f;   // rsm wave-uniform and rare
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, o), rD, q * 4, e0 * HW * 4, 0);
@@ -807,6 +868,14 @@ void core_group_kernel(CoreStepArgs a) {
 #pragma unroll
         for (int k = 0; k < (SCALAR_TAIL ? NSF : NS); k++) {
             const int tb = toff[k];
+            // PEP: c0 / c1 of the slot's env (senv, not the lane's agent's env), taken with every lane
+            // active; a missing slot's senv (15) names a lane whose record load was dropped: zeros
+            float c0 = a.c0, c1 = a.c1;
+            if constexpr (PEP) {
+                const int se = (int)((geo >> (8 + 4 * k)) & 15u);
+                c0 = env_val(cur.pr.z, se);
+                c1 = env_val(cur.pr.w, se);
+            }
             if (k >= NSF && tb < 0) continue;
             const bool yl = ((geo >> (2 * k)) & 1u) != 0u, yr = ((geo >> (2 * k)) & 2u) != 0u;
             const float* p = tile + tb;
@@ -814,11 +883,11 @@ void core_group_kernel(CoreStepArgs a) {
 #pragma unroll
             for (int dx = -1; dx <= 1; dx++) {
                 const float4 u = *reinterpret_cast<const float4*>(p + dx * W);
-                b[dx + 1][1] = a.c0 * u.x; b[dx + 1][2] = a.c0 * u.y;
-                b[dx + 1][3] = a.c0 * u.z; b[dx + 1][4] = a.c0 * u.w;
+                b[dx + 1][1] = c0 * u.x; b[dx + 1][2] = c0 * u.y;
+                b[dx + 1][3] = c0 * u.z; b[dx + 1][4] = c0 * u.w;
                 if (NB == 4 && dx != 0) continue;
-                b[dx + 1][0] = a.c0 * tile[NB == 4 ? lo[k] : yl ? 0 : tb + dx * W - 1];   // tile[0] == 0
-                b[dx + 1][5] = a.c0 * tile[NB == 4 ? ro[k] : yr ? 0 : tb + dx * W + 4];
+                b[dx + 1][0] = c0 * tile[NB == 4 ? lo[k] : yl ? 0 : tb + dx * W - 1];   // tile[0] == 0
+                b[dx + 1][5] = c0 * tile[NB == 4 ? ro[k] : yr ? 0 : tb + dx * W + 4];
             }
             if (NB == 8 && ONE) {
                 // Moore, straight-line form: pin every B value to a register.  Without the loop
@@ -835,7 +904,7 @@ void core_group_kernel(CoreStepArgs a) {
                 float acc = b[1][jj + 1];
 #pragma unroll
                 for (int d = 0; d < NB; d++) {
-                    const float t = a.c1 * b[1 + nb_dx<NB>(d)][jj + 1 + nb_dy<NB>(d)];   // :113
+                    const float t = c1 * b[1 + nb_dx<NB>(d)][jj + 1 + nb_dy<NB>(d)];   // :113
                     acc = acc + t;
                 }
                 o[jj] = acc < 1e-4f ? 0.0f : acc;                                     // :116-117
@@ -856,9 +925,8 @@ void core_group_kernel(CoreStepArgs a) {
             while (m) {
                 const long long e = (long long)e0 + __builtin_ctz(m);
                 m &= m - 1u;
-                wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane);
-                if (FFM_GROUP_ABLATE & 1)   // diagnostic: the same placement again (identical result)
-                    wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane);
+                place(e);
+                if (FFM_GROUP_ABLATE & 1) place(e);   // diagnostic: the same placement again (identical result)
             }
             break;
         }
@@ -877,9 +945,8 @@ void core_group_kernel(CoreStepArgs a) {
             const long long e = (long long)(g_first + (bit >> 3) * wstride) * G + (bit & 7);
             // at most (H - 2) * (W - 2) cells are free: the placement's small-list path only
             static_assert((H - 2) * (W - 2) <= 128, "wave_reset_env<.., SMALL>");
-            wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane);
-            if (FFM_GROUP_ABLATE & 1)   // diagnostic: the same placement again (identical result)
-                wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane);
+            place(e);
+            if (FFM_GROUP_ABLATE & 1) place(e);   // diagnostic: the same placement again (identical result)
         }
     }
 
@@ -918,6 +985,7 @@ size_t core_group_stage_bytes(int H, int W, int F) {
 // The image on the host.  The SFF term is the one f32 product the kernel used to stage per launch,
 // f32(-k_S) * SFF: a single IEEE multiply (this file is built without contraction), so the bits
 // are the device's.
+// kS32 = 1.0f gives the per-env forms' image: the product is exact, the region holds the SFF's own bits.
 void core_group_stage_build(int H, int W, int F, const uint8_t* pmap, const float* psff, float kS32,
                             const uint16_t* free_padded, unsigned char* out) {
     const int PHW = (H + 2) * (W + 2);
@@ -949,15 +1017,16 @@ void core_group_stage_build(int H, int W, int F, const uint8_t* pmap, const floa
 
 // KD1: k_D == 1 (the drivers' setting), where k_D * DFF is DFF itself: a kernel of its own
 // rather than a runtime flag, which the register allocator would keep (and spill) all launch.
-template <int NB, bool KD1, int G>
+// PEP: the per-env form (a.envp set; a.stage is then the image built with multiplier 1).
+template <int NB, bool KD1, int G, bool PEP = false>
 static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int op, int* occ, bool one) {
     // each form at its own LDS size
     const size_t smem = core_group_smem_bytes(a.H, a.W, a.F, 4, G), smem1 = core_group_smem_bytes(a.H, a.W, a.F, 4, G, true);
     if (op) {   // the resident blocks per CU of the form `one` names
         *occ = 0;
         const hipError_t r =
-            one ? hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1, false, true>, 256, smem1)
-                : hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1, false, false>, 256, smem);
+            one ? hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1, false, true, PEP>, 256, smem1)
+                : hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1, false, false, PEP>, 256, smem);
         if (r != hipSuccess) *occ = 0;
         return hipSuccess;
     }
@@ -970,17 +1039,20 @@ static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int
     // the single-group form wherever no wave of the grid steps a second group
     const dim3 grid((unsigned)blocks), block(256);
     if (one && core_group_one_group(a.E, blocks, G)) {
-        if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true, true><<<grid, block, smem1, s>>>(a);
-        else core_group_kernel<NB, 12, 12, G, KD1, false, true><<<grid, block, smem1, s>>>(a);
+        if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true, true, PEP><<<grid, block, smem1, s>>>(a);
+        else core_group_kernel<NB, 12, 12, G, KD1, false, true, PEP><<<grid, block, smem1, s>>>(a);
     } else {
-        if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true, false><<<grid, block, smem, s>>>(a);
-        else core_group_kernel<NB, 12, 12, G, KD1, false, false><<<grid, block, smem, s>>>(a);
+        if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true, false, PEP><<<grid, block, smem, s>>>(a);
+        else core_group_kernel<NB, 12, 12, G, KD1, false, false, PEP><<<grid, block, smem, s>>>(a);
     }
     return hipGetLastError();
 }
 
 template <int NB>
 static hipError_t group_op_kd(const CoreStepArgs& a, int blocks, hipStream_t s, int op, int* occ, int G, bool one) {
+    if (a.envp)   // per-env parameters: every env's own k_D, so no KD1 variant
+        return G == kGroupGSmall ? group_op<NB, false, kGroupGSmall, true>(a, blocks, s, op, occ, one)
+                                 : group_op<NB, false, kGroupG, true>(a, blocks, s, op, occ, one);
     if (G == kGroupGSmall)
         return a.kD32 == 1.0f ? group_op<NB, true, kGroupGSmall>(a, blocks, s, op, occ, one)
                               : group_op<NB, false, kGroupGSmall>(a, blocks, s, op, occ, one);
@@ -998,6 +1070,7 @@ hipError_t launch_core_group(const CoreStepArgs& a, int nb, int blocks, hipStrea
 }
 
 // one: of the single-group form (diagnostic); the grid rules count with the loop form's.
+// a.envp set: of the per-env forms.
 int core_group_blocks_per_cu(const CoreStepArgs& a, int nb, int G, bool one) {
     int n = 0;
     (void)(nb == 4 ? group_op_kd<4>(a, 0, nullptr, 1, &n, G, one) : group_op_kd<8>(a, 0, nullptr, 1, &n, G, one));

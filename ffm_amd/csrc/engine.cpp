@@ -106,24 +106,38 @@ struct ffm_engine {
     hipEvent_t sh_fork = nullptr;
     hipEvent_t sh_end[3] = {nullptr, nullptr, nullptr};
     // Per-env parameters (ffm_engine_set_env_params): null / empty while off.  While on, an
-    // engine of the group kernel steps with the lane kernel and one of the wave kernel with the
-    // block kernel (neither has a per-env form); the others keep their kernel.
+    // engine of the group kernel steps with the lane kernel's per-env form, or, if asked
+    // (ffm_engine_set_env_params_kernel), with the group kernel's own; one of the wave kernel
+    // steps with the block kernel (it has no per-env form); the others keep their kernel.
     ffm::EnvParams* d_envp = nullptr;          // [n_envs] records (kernels.h)
     std::vector<ffm_env_params> pep_sets;      // the caller's tables, for ffm_engine_get_env_params
     std::vector<int32_t> pep_set_of_env;
     bool pep_lane = false;                     // step with the lane kernel
     int pep_lane_blocks = 0;                   // its persistent grid
+    int pep_kernel = 0;                        // ffm_engine_set_env_params_kernel's mode (sticky)
+    bool pep_group = false;                    // step with the group kernel's per-env form (mode 1, feature on)
+    int pep_group_blocks = 0, pep_group_g = 4; // its grid and envs per group, from that form's occupancy
+    std::vector<Shard> pep_shards;             // ... and its step shards (size() <= 1: off)
+    unsigned char* d_stage_raw = nullptr;      // its stage image: the SFF term with multiplier 1 (the raw SFF);
+                                               // built when the feature first moves to the group kernel
 };
 
 // The kernel that steps the engine under its current settings (per-env parameters move group and
 // wave engines): at most one of these holds, none means the block kernel.
-static bool steps_group(const ffm_engine* e) { return e->group && !e->d_envp; }
-static bool steps_lane(const ffm_engine* e) { return e->d_envp ? e->pep_lane : e->lane; }
+static bool pep_group_on(const ffm_engine* e) { return e->d_envp && e->pep_group; }
+static bool steps_group(const ffm_engine* e) { return e->group && (!e->d_envp || e->pep_group); }
+static bool steps_lane(const ffm_engine* e) { return e->d_envp ? e->pep_lane && !e->pep_group : e->lane; }
 static bool steps_wave(const ffm_engine* e) { return e->wave && !e->d_envp; }
 // Blocks per CU of the group kernel's largest grid (engine create, group_grid).
 constexpr int kGroupGridPerCu = 8;
 
 static int lane_blocks_now(const ffm_engine* e) { return e->d_envp ? e->pep_lane_blocks : e->lane_blocks; }
+// The group kernel's launch geometry in effect: the create-time one, or the per-env form's.
+static int group_blocks_now(const ffm_engine* e) { return pep_group_on(e) ? e->pep_group_blocks : e->group_blocks; }
+static int group_g_now(const ffm_engine* e) { return pep_group_on(e) ? e->pep_group_g : e->group_g; }
+static const std::vector<ffm_engine::Shard>& shards_now(const ffm_engine* e) {
+    return pep_group_on(e) ? e->pep_shards : e->shards;
+}
 
 // The lane kernel's persistent grid for n_envs envs (a.envp set: of its per-env form).
 static int lane_grid(const ffm::CoreStepArgs& a, int nb, long long n_envs, int cus) {
@@ -167,6 +181,92 @@ static void free_episode_log(ffm_engine* e, bool ep_start_too) {
     }
 }
 
+// The group kernel's launch geometry for n_envs envs: envs per group, the one-launch grid and the
+// step shards (empty: one launch per step), from the resident blocks of the kernel form `a` names
+// (a.envp set: the per-env form).
+struct GroupGeom {
+    int g = 4, blocks = 0;
+    std::vector<ffm_engine::Shard> shards;
+    size_t shard_slots = 0;   // counter slots of the step shards, one range each
+};
+static GroupGeom group_geometry(const ffm::CoreStepArgs& a, int nb, long long n_envs, int cus) {
+    GroupGeom gg;
+    // The loop form's resident blocks, at most 6 (6 waves per SIMD) per CU: what the shard
+    // rule and the group-size picker count with (as a one-launch grid, 7 per CU stepped
+    // slower and so did fewer than 6: profiles/r06/c2/ab_grid_balance*.log,
+    // ab_occupancy7.log).
+    auto resident_cap = [&](int G) {
+        const int per_cu = std::max(1, ffm::core_group_blocks_per_cu(a, nb, G));
+        return (long long)cus * std::min(per_cu, 6);
+    };
+    // The grid of a launch of n envs: a wave per group up to kGroupGridPerCu blocks per CU
+    // (2,048 on MI355X: each of the headline's two shards of 8,192 groups then takes the
+    // single-group form, whose 56 VGPRs and 22.4 KB of LDS keep 7 blocks per CU
+    // resident; profiles/one_group/), the persistent loop beyond.
+    auto group_grid = [&](long long n, int G) {
+        const long long groups = (n + G - 1) / G;
+        long long b = std::max<long long>(1, std::min<long long>((groups + 3) / 4, (long long)cus * kGroupGridPerCu));
+        if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {   // diagnostic override of the grid
+            const long long v = std::atoll(ov);
+            if (v > 0) b = std::min<long long>(v, (groups + 3) / 4);
+        }
+        // every wave steps at most core_group_max_iters() groups (its deferred-reset mask)
+        const long long per_wave = ffm::core_group_max_iters();
+        return (int)std::max<long long>(b, (groups + 4 * per_wave - 1) / (4 * per_wave));
+    };
+    gg.g = ffm::core_group_pick_envs(a, nb, n_envs, cus);
+    gg.blocks = group_grid(n_envs, gg.g);
+
+    // Step shards.  FFM_STEP_SHARDS=1..4 forces the count (A/B switch, read at create and when
+    // the per-env form's geometry is taken);
+    // unset, kDefaultStepShards shards wherever the one-launch grid has its waves step two
+    // or more groups (on MI355X from 24,577 envs on; two shards measured faster from
+    // 8,192 envs on, but below that size the engine keeps the single launch its callers
+    // and the geometry tests know).  Every shard launches the persistent grid its env
+    // count would get alone: the shards alternate on the GPU, and the slots a draining
+    // launch frees take the next shard's blocks (1 / S of the resident blocks per shard
+    // measured slower: profiles/step_shards/).
+    int S = kDefaultStepShards;
+    const long long groups = (n_envs + gg.g - 1) / gg.g;
+    if (groups <= resident_cap(gg.g) * 4) S = 1;
+    if (const char* ov = std::getenv("FFM_STEP_SHARDS")) {
+        const int v = std::atoi(ov);
+        if (v >= 1 && v <= kMaxStepShards) S = v;
+    }
+    if (S > 1) {
+        // contiguous shards whose boundaries are multiples of 8 envs: only the last can
+        // hold a partial group, whose stores land in the arrays' zeroed padding
+        // (core_group.hip); empty shards are skipped
+        const long long per = ((n_envs + S - 1) / S + 7) & ~7ll;
+        size_t ctr0 = 0;
+        for (long long e0 = 0; e0 < n_envs; e0 += per) {
+            ffm_engine::Shard sh;
+            sh.e0 = e0;
+            sh.n = std::min<long long>(per, n_envs - e0);
+            sh.g = ffm::core_group_pick_envs(a, nb, sh.n, cus);
+            sh.blocks = group_grid(sh.n, sh.g);
+            sh.ctr0 = ctr0;           // a slot range per shard: never contended on the device
+            ctr0 += (size_t)sh.blocks * 4;
+            gg.shards.push_back(sh);
+        }
+        gg.shard_slots = ctr0;
+        if (gg.shards.size() <= 1) gg.shards.clear();
+    }
+    return gg;
+}
+
+// The shards' streams (shard 0 runs on the caller's) and the fork / join events, for n shards;
+// what exists already is kept.
+static hipError_t ensure_shard_streams(ffm_engine* e, size_t n) {
+    hipError_t he = hipSuccess;
+    if (n > 1 && !e->sh_fork) he = hipEventCreateWithFlags(&e->sh_fork, hipEventDisableTiming);
+    for (size_t i = 0; he == hipSuccess && i + 1 < n; i++) {
+        if (!e->sh_stream[i]) he = hipStreamCreateWithFlags(&e->sh_stream[i], hipStreamNonBlocking);
+        if (he == hipSuccess && !e->sh_end[i]) he = hipEventCreateWithFlags(&e->sh_end[i], hipEventDisableTiming);
+    }
+    return he;
+}
+
 static void free_capture(ffm_engine* e) {
     void* bufs[] = {(void*)e->cap.envs, (void*)e->cap.phase, e->cap.state, e->cap.meta, e->cap.cells, e->cap.n};
     for (void* p : bufs) (void)hipFree(p);
@@ -193,6 +293,7 @@ static void release(ffm_engine* e) {
     (void)hipFree(e->d_free);
     (void)hipFree(e->d_free_padded);
     (void)hipFree(e->d_stage);
+    (void)hipFree(e->d_stage_raw);
     (void)hipFree(e->d_pos);
     (void)hipFree(e->d_cnt);
     (void)hipFree(e->d_dff);
@@ -389,70 +490,15 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
             }
         }
         if (e->group) {
-            // The loop form's resident blocks, at most 6 (6 waves per SIMD) per CU: what the shard
-            // rule and the group-size picker count with (as a one-launch grid, 7 per CU stepped
-            // slower and so did fewer than 6: profiles/r06/c2/ab_grid_balance*.log,
-            // ab_occupancy7.log).
-            auto resident_cap = [&](int G) {
-                const int per_cu = std::max(1, ffm::core_group_blocks_per_cu(a, d.neighborhood, G));
-                return (long long)cus * std::min(per_cu, 6);
-            };
             // FFM_GROUP_ONE=0|1 (A/B and test switch, read at create): 0 keeps the loop form of
             // the group kernel on every grid; unset or 1, a launch whose waves step at most one
             // group each takes the single-group form (core_group.hip, ONE)
             if (const char* ov = std::getenv("FFM_GROUP_ONE")) e->group_one = std::atoi(ov) != 0;
-            // The grid of a launch of n envs: a wave per group up to kGroupGridPerCu blocks per CU
-            // (2,048 on MI355X: each of the headline's two shards of 8,192 groups then takes the
-            // single-group form, whose 56 VGPRs and 22.4 KB of LDS keep 7 blocks per CU
-            // resident; profiles/one_group/), the persistent loop beyond.
-            auto group_grid = [&](long long n, int G) {
-                const long long groups = (n + G - 1) / G;
-                long long b = std::max<long long>(1, std::min<long long>((groups + 3) / 4, (long long)cus * kGroupGridPerCu));
-                if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {   // diagnostic override of the grid
-                    const long long v = std::atoll(ov);
-                    if (v > 0) b = std::min<long long>(v, (groups + 3) / 4);
-                }
-                // every wave steps at most core_group_max_iters() groups (its deferred-reset mask)
-                const long long per_wave = ffm::core_group_max_iters();
-                return (int)std::max<long long>(b, (groups + 4 * per_wave - 1) / (4 * per_wave));
-            };
-            e->group_g = ffm::core_group_pick_envs(a, d.neighborhood, d.n_envs, cus);
-            e->group_blocks = group_grid(d.n_envs, e->group_g);
-
-            // Step shards.  FFM_STEP_SHARDS=1..4 forces the count (A/B switch, read at create);
-            // unset, kDefaultStepShards shards wherever the one-launch grid has its waves step two
-            // or more groups (on MI355X from 24,577 envs on; two shards measured faster from
-            // 8,192 envs on, but below that size the engine keeps the single launch its callers
-            // and the geometry tests know).  Every shard launches the persistent grid its env
-            // count would get alone: the shards alternate on the GPU, and the slots a draining
-            // launch frees take the next shard's blocks (1 / S of the resident blocks per shard
-            // measured slower: profiles/step_shards/).
-            int S = kDefaultStepShards;
-            const long long groups = (d.n_envs + e->group_g - 1) / e->group_g;
-            if (groups <= resident_cap(e->group_g) * 4) S = 1;
-            if (const char* ov = std::getenv("FFM_STEP_SHARDS")) {
-                const int v = std::atoi(ov);
-                if (v >= 1 && v <= kMaxStepShards) S = v;
-            }
-            if (S > 1) {
-                // contiguous shards whose boundaries are multiples of 8 envs: only the last can
-                // hold a partial group, whose stores land in the arrays' zeroed padding
-                // (core_group.hip); empty shards are skipped
-                const long long per = ((d.n_envs + S - 1) / S + 7) & ~7ll;
-                size_t ctr0 = 0;
-                for (long long e0 = 0; e0 < d.n_envs; e0 += per) {
-                    ffm_engine::Shard sh;
-                    sh.e0 = e0;
-                    sh.n = std::min<long long>(per, d.n_envs - e0);
-                    sh.g = ffm::core_group_pick_envs(a, d.neighborhood, sh.n, cus);
-                    sh.blocks = group_grid(sh.n, sh.g);
-                    sh.ctr0 = ctr0;           // a slot range per shard: never contended on the device
-                    ctr0 += (size_t)sh.blocks * 4;
-                    e->shards.push_back(sh);
-                }
-                shard_slots = ctr0;
-                if (e->shards.size() <= 1) e->shards.clear();
-            }
+            GroupGeom gg = group_geometry(a, d.neighborhood, d.n_envs, cus);
+            e->group_g = gg.g;
+            e->group_blocks = gg.blocks;
+            e->shards = std::move(gg.shards);
+            shard_slots = gg.shard_slots;
         }
     }
     // One counter slot per wave (wave / lane kernel) or block (block kernel):
@@ -467,11 +513,7 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
     }
     // the shards' streams (shard 0 runs on the caller's) and the fork / join events
     if (!e->shards.empty()) {
-        he = hipEventCreateWithFlags(&e->sh_fork, hipEventDisableTiming);
-        for (size_t i = 0; he == hipSuccess && i + 1 < e->shards.size(); i++) {
-            he = hipStreamCreateWithFlags(&e->sh_stream[i], hipStreamNonBlocking);
-            if (he == hipSuccess) he = hipEventCreateWithFlags(&e->sh_end[i], hipEventDisableTiming);
-        }
+        he = ensure_shard_streams(e, e->shards.size());
         if (he != hipSuccess)
             return cleanup(fail(FFM_E_HIP, std::string("step shard streams: ") + hipGetErrorString(he)));
     }
@@ -553,7 +595,7 @@ static ffm::CoreStepArgs make_args(ffm_engine* e) {
     a.free_padded = e->d_free_padded;
     a.F = e->F;
     a.reset_thr = e->reset_thr;
-    a.stage = e->d_stage;
+    a.stage = pep_group_on(e) ? e->d_stage_raw : e->d_stage;   // the per-env form takes k_S from the records
     a.stage_q4 = e->stage_q4;
     a.mt_np = e->d_mt_np;
     a.mt_py = e->d_mt_py;
@@ -573,11 +615,12 @@ static ffm::CoreStepArgs make_args(ffm_engine* e) {
 
 // Shards a step(n > 1) call runs as, under the engine's current settings: 1 (one launch per
 // step over all envs) with trajectory capture on (its kernel follows every step launch on the
-// caller's stream), on the fused multi-step path and with per-env parameters (the shards belong
-// to the group kernel).
+// caller's stream), on the fused multi-step path and with per-env parameters on the lane kernel
+// (the shards belong to the group kernel; on its per-env form they are that form's own).
 static int shards_in_effect(const ffm_engine* e) {
-    if (e->shards.size() <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi) || e->d_envp) return 1;
-    return (int)e->shards.size();
+    const std::vector<ffm_engine::Shard>& sh = shards_now(e);
+    if (sh.size() <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi) || !steps_group(e)) return 1;
+    return (int)sh.size();
 }
 
 // n_steps steps as one launch per step and shard.  One fork and one join per call: the shard
@@ -587,7 +630,8 @@ static int shards_in_effect(const ffm_engine* e) {
 // of that shard only (envs are independent, every draw is keyed by (t, global env)).  Whatever
 // else the engine enqueues uses the caller's stream and is ordered by the join.
 static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
-    const size_t S = e->shards.size();
+    const std::vector<ffm_engine::Shard>& shards = shards_now(e);
+    const size_t S = shards.size();
     const int A = e->d.agent_capacity;
     HIP_TRY(hipEventRecord(e->sh_fork, s));
     for (size_t k = 1; k < S; k++) HIP_TRY(hipStreamWaitEvent(e->sh_stream[k - 1], e->sh_fork, 0));
@@ -596,7 +640,7 @@ static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
     int done = 0;
     for (; done < n_steps && he == hipSuccess; done++) {
         for (size_t k = 0; k < S && he == hipSuccess; k++) {
-            const ffm_engine::Shard& sh = e->shards[k];
+            const ffm_engine::Shard& sh = shards[k];
             ffm::CoreStepArgs a = base;
             a.t = e->t + (uint32_t)done;
             a.E = sh.n;
@@ -606,6 +650,7 @@ static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
             a.dff = base.dff + sh.e0 * e->HW;
             a.episodes = base.episodes + sh.e0;
             if (base.ep_start) a.ep_start = base.ep_start + sh.e0;   // records carry global ids through env_base
+            if (base.envp) a.envp = base.envp + sh.e0;
             a.counters = base.counters + 4 * sh.ctr0;
             a.no_step_count = k != 0;   // one shard per step counts the step
             he = ffm::launch_core_group(a, e->d.neighborhood, sh.blocks, k ? e->sh_stream[k - 1] : s, sh.g, e->group_one);
@@ -650,7 +695,7 @@ int ffm_engine_step(ffm_engine* e, int32_t n_steps, void* stream) {
     }
     for (int i = 0; i < n_steps; i++) {
         ffm::CoreStepArgs a = make_args(e);
-        if (steps_group(e)) HIP_TRY(ffm::launch_core_group(a, e->d.neighborhood, e->group_blocks, s, e->group_g, e->group_one));
+        if (steps_group(e)) HIP_TRY(ffm::launch_core_group(a, e->d.neighborhood, group_blocks_now(e), s, group_g_now(e), e->group_one));
         else if (steps_lane(e)) HIP_TRY(ffm::launch_core_lane(a, e->d.neighborhood, lane_blocks_now(e), s));
         else if (steps_wave(e)) HIP_TRY(ffm::launch_core_wave(a, e->d.neighborhood, e->mt, e->wave_blocks, s));
         else HIP_TRY(ffm::launch_core_block(a, e->d.neighborhood, e->f64, e->mt, e->block, s));
@@ -973,6 +1018,67 @@ int ffm_engine_get_episode_stats(ffm_engine* e, uint64_t* hist, int32_t bins, ui
     return FFM_OK;
 }
 
+// What the group kernel's per-env form needs beyond the records: its stage image (built once:
+// the create-time image with the SFF term's multiplier 1, so the LDS region holds the raw SFF) and
+// its launch geometry, sized from that form's occupancy (envp: any non-null pointer, it only
+// selects the form).  Fills the pep_group_* fields; the caller sets pep_group.
+static int pep_group_setup(ffm_engine* e, const ffm::EnvParams* envp) {
+    const int H = e->d.H, W = e->d.W, PHW = (H + 2) * (W + 2);
+    HIP_TRY(hipSetDevice(e->d.device));
+    if (!e->d_stage_raw) {
+        std::vector<uint8_t> pmap((size_t)PHW);
+        std::vector<float> psff((size_t)PHW);
+        std::vector<uint16_t> fp((size_t)std::max(1, e->F));
+        HIP_TRY(hipMemcpy(pmap.data(), e->d_map, (size_t)PHW, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(psff.data(), e->d_sff, (size_t)PHW * 4, hipMemcpyDeviceToHost));
+        if (e->F > 0) HIP_TRY(hipMemcpy(fp.data(), e->d_free_padded, (size_t)e->F * 2, hipMemcpyDeviceToHost));
+        std::vector<unsigned char> img(e->stage_bytes);
+        ffm::core_group_stage_build(H, W, e->F, pmap.data(), psff.data(), 1.0f, fp.data(), img.data());
+        unsigned char* buf = nullptr;
+        if (hipMalloc((void**)&buf, e->stage_bytes) != hipSuccess) return fail(FFM_E_NOMEM, "env params: stage image");
+        const hipError_t he = hipMemcpy(buf, img.data(), img.size(), hipMemcpyHostToDevice);
+        if (he != hipSuccess) {
+            (void)hipFree(buf);
+            return fail(FFM_E_HIP, std::string("env params: stage image: ") + hipGetErrorString(he));
+        }
+        e->d_stage_raw = buf;
+    }
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->d.device));
+    ffm::CoreStepArgs a{};
+    a.H = H; a.W = W; a.A = e->d.agent_capacity; a.F = e->F; a.auto_reset = e->d.auto_reset;
+    a.envp = envp;   // the occupancy of the per-env form
+    GroupGeom gg = group_geometry(a, e->d.neighborhood, e->d.n_envs, cus);
+    // The counter slots were sized at create.  A geometry that needs more (the per-env form
+    // resident in other numbers than the create-time form, so another group size or shard count)
+    // gives way to the create-time one, which is valid for every form.
+    if (std::max((size_t)gg.blocks * 4, gg.shard_slots) > e->ctr_slots) {
+        gg.g = e->group_g;
+        gg.blocks = e->group_blocks;
+        gg.shards = e->shards;
+    }
+    const hipError_t he = ensure_shard_streams(e, gg.shards.size());
+    if (he != hipSuccess) return fail(FFM_E_HIP, std::string("step shard streams: ") + hipGetErrorString(he));
+    e->pep_group_g = gg.g;
+    e->pep_group_blocks = gg.blocks;
+    e->pep_shards = std::move(gg.shards);
+    return FFM_OK;
+}
+
+int ffm_engine_set_env_params_kernel(ffm_engine* e, int32_t mode) {
+    if (!e) return fail(FFM_E_INVALID, "null engine");
+    if (mode != 0 && mode != 1) return fail(FFM_E_INVALID, "env params kernel: mode must be 0 (lane) or 1 (group)");
+    if (mode == 1 && (!e->group || e->mt))
+        return fail(FFM_E_UNSUPPORTED, "env params kernel: the engine was not created on the group kernel");
+    if (mode == 1 && e->d_envp && !e->pep_group) {   // the feature is on: move it now
+        const int rc = pep_group_setup(e, e->d_envp);
+        if (rc) return rc;
+    }
+    e->pep_kernel = mode;
+    e->pep_group = mode == 1 && e->d_envp != nullptr;
+    return FFM_OK;
+}
+
 int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t n_sets, const int32_t* set_of_env,
                               void* stream) {
     if (!e) return fail(FFM_E_INVALID, "null engine");
@@ -988,6 +1094,8 @@ int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t
         e->pep_set_of_env.clear();
         e->pep_lane = false;
         e->pep_lane_blocks = 0;
+        e->pep_group = false;
+        e->pep_shards.clear();
         return FFM_OK;
     }
     if (!sets || !set_of_env) return fail(FFM_E_INVALID, "env params: sets and set_of_env are required");
@@ -1046,6 +1154,12 @@ int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t
         a.envp = buf;   // the occupancy of the per-env form
         lane_blocks = lane_grid(a, nb, e->d.n_envs, cus);
     }
+    // the group kernel's own per-env form, if that is the engine's setting
+    const bool to_group = e->pep_kernel == 1 && e->group;
+    if (to_group && !e->pep_group) {
+        const int rc = pep_group_setup(e, buf);
+        if (rc) return undo(rc);
+    }
     // stream-ordered after the steps queued so far; the tables are consumed before the return
     hipError_t he = hipMemcpyAsync(buf, rec.data(), E * sizeof(ffm::EnvParams), hipMemcpyHostToDevice, s);
     if (he == hipSuccess) he = hipStreamSynchronize(s);
@@ -1055,6 +1169,7 @@ int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t
     e->pep_set_of_env.assign(set_of_env, set_of_env + E);
     e->pep_lane = lane;
     e->pep_lane_blocks = lane_blocks;
+    e->pep_group = to_group;
     return FFM_OK;
 }
 
@@ -1134,8 +1249,9 @@ int ffm_debug_group_occupancy(ffm_engine* e, int32_t one, int32_t* blocks_per_cu
     *blocks_per_cu = 0;
     if (!e->group) return FFM_OK;
     HIP_TRY(hipSetDevice(e->d.device));
-    const ffm::CoreStepArgs a = make_args(e);
-    *blocks_per_cu = ffm::core_group_blocks_per_cu(a, e->d.neighborhood, e->group_g, one != 0);
+    ffm::CoreStepArgs a = make_args(e);
+    if (!pep_group_on(e)) a.envp = nullptr;   // the form that steps the engine (the per-env one only while it does)
+    *blocks_per_cu = ffm::core_group_blocks_per_cu(a, e->d.neighborhood, group_g_now(e), one != 0);
     return FFM_OK;
 }
 
@@ -1148,7 +1264,7 @@ int ffm_debug_reset_candidates(ffm_engine* e, int32_t* m, uint32_t* thr) {
 }
 
 // Diagnostic (not part of the ABI header): the launch geometry in effect (chosen at create; with
-// per-env parameters on, the kernel and grid that step the engine meanwhile).
+// per-env parameters on, the kernel, grid and shards that step the engine meanwhile).
 //   out[0] step kernel (0 group, 1 lane, 2 wave, 3 block, 4 block with global scratch)
 //   out[1] envs per group of the group kernel (0 for the other kernels)
 //   out[2] blocks of the step kernel's grid
@@ -1166,24 +1282,24 @@ int ffm_debug_launch_info(ffm_engine* e, int32_t* out, int n) {
     const int kernel = group ? 0 : lane ? 1 : wave ? 2 : e->big ? 4 : 3;
     const long long E = e->d.n_envs;
     const int S = shards_in_effect(e);
-    const int32_t step_blocks = group ? e->group_blocks : lane ? lane_blocks_now(e) : wave ? e->wave_blocks
+    const int32_t step_blocks = group ? group_blocks_now(e) : lane ? lane_blocks_now(e) : wave ? e->wave_blocks
                                                                                         : (int32_t)((E + e->K - 1) / e->K);
     bool one = group && e->group_one;
     if (one && S > 1) {
-        for (const ffm_engine::Shard& sh : e->shards) one = one && ffm::core_group_one_group(sh.n, sh.blocks, sh.g);
+        for (const ffm_engine::Shard& sh : shards_now(e)) one = one && ffm::core_group_one_group(sh.n, sh.blocks, sh.g);
     } else if (one) {
-        one = ffm::core_group_one_group(E, e->group_blocks, e->group_g);
+        one = ffm::core_group_one_group(E, group_blocks_now(e), group_g_now(e));
     }
     const int32_t v[10] = {
         kernel,
-        group ? e->group_g : 0,
+        group ? group_g_now(e) : 0,
         step_blocks,
         e->K,
         kernel <= 2 ? 256 : e->big ? 1024 : e->block,
         e->multi ? 1 : 0,
         e->multi ? e->multi_blocks : 0,
         S,
-        S > 1 ? e->shards[0].blocks : step_blocks,
+        S > 1 ? shards_now(e)[0].blocks : step_blocks,
         one ? 1 : 0,
     };
     for (int i = 0; i < n; i++) out[i] = v[i];

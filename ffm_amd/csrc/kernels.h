@@ -61,7 +61,9 @@ struct CoreStepArgs {
                               // the threshold then holds a scalar register across the whole step loop.)
     // Group kernel: the engine-constant stage image (core_group_stage_build; 16-B aligned).  Its
     // first stage_q4 float4s are the block-shared LDS region byte for byte; the per-lane geometry
-    // tables of both group sizes follow.  Built once at create: nothing in it has a setter.
+    // tables of both group sizes follow.  Built once at create: nothing in it has a setter.  The
+    // group kernel's per-env forms (envp set) take a second image, built with multiplier 1 for the
+    // SFF term: every env's own k_S is applied in the kernel.
     const void* stage;
     int stage_q4;
     // Episode log and statistics (ffm_engine_set_episode_log; episode_log.h).  All null / zero

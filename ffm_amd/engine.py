@@ -31,7 +31,7 @@ EXPORTED = [
     "ffm_engine_set_trajectory_capture", "ffm_engine_drain_trajectory",
     "ffm_engine_set_episode_log", "ffm_engine_drain_episodes", "ffm_engine_get_episode_stats",
     "ffm_debug_stage_image", "ffm_debug_reset_candidates",
-    "ffm_engine_set_env_params", "ffm_engine_get_env_params",
+    "ffm_engine_set_env_params", "ffm_engine_get_env_params", "ffm_engine_set_env_params_kernel",
     "ffm_learner_create", "ffm_learner_destroy", "ffm_learner_reset", "ffm_learner_reset_envs", "ffm_learner_step",
     "ffm_learner_set_state", "ffm_learner_get_state", "ffm_learner_get_episodes",
     "ffm_learner_set_mt_state", "ffm_learner_get_mt_state", "ffm_learner_get_counters",
@@ -151,6 +151,7 @@ def load_library():
     L.ffm_engine_get_episode_stats.argtypes = [P, P, i32, P, i32, P]
     L.ffm_engine_set_env_params.argtypes = [P, C.POINTER(EnvParams), i32, P, P]
     L.ffm_engine_get_env_params.argtypes = [P, C.POINTER(EnvParams), i32, C.POINTER(i32), P]
+    L.ffm_engine_set_env_params_kernel.argtypes = [P, i32]
     L.ffm_np_expf_device.argtypes = [P, P, i64, P]
     L.ffm_debug_stage_image.argtypes = [P, P, i64, C.POINTER(i64)]
     L.ffm_debug_reset_candidates.argtypes = [P, C.POINTER(i32), C.POINTER(C.c_uint32)]
@@ -382,17 +383,28 @@ class Engine:
         _check(self._L.ffm_engine_update_dff(self._h, _stream_handle(stream)))
 
     # -- per-env parameters ----------------------------------------------------
-    def set_env_params(self, sets, set_of_env=None, stream=None):
+    _ENV_PARAMS_KERNELS = {"lane": 0, "group": 1}
+
+    def set_env_params(self, sets, set_of_env=None, stream=None, kernel=None):
         """A sweep in one engine (ffm_engine_set_env_params): env e takes sets[set_of_env[e]] and
         from the next step on evolves bit for bit like the env with the same global id of an
         engine created with that set.  `sets`: dicts with any of k_S, k_D, diffuse, decay,
         n_agents (missing keys: the engine's create-time values); `set_of_env`: n_envs indices
         into it (default arange(n_envs) % len(sets)).  A new n_agents holds from the env's next
         placement (reset, reset_envs, auto-reset).  sets=None or []: off -- back to the
-        create-time parameters, kernel and launch geometry.  While on, a "group" engine steps
-        with the lane kernel and a "wave" engine with the block kernel (launch_info())."""
+        create-time parameters, kernel and launch geometry.  While on, a "wave" engine steps
+        with the block kernel and a "group" engine with the lane kernel, or, with
+        kernel="group", with the group kernel's own per-env form and its step shards
+        (launch_info()).  `kernel`: "lane", "group" or None (the engine's setting, "lane" at
+        create, stays); sticky (ffm_engine_set_env_params_kernel).  "group" on an engine not
+        created on the group kernel raises NotImplementedError and changes nothing."""
+        if kernel is not None and kernel not in self._ENV_PARAMS_KERNELS:
+            raise ValueError(f"kernel must be None, 'lane' or 'group', got {kernel!r}")
         sets = list(sets) if sets is not None else []
         if not sets:
+            if kernel is not None:
+                _check(self._L.ffm_engine_set_env_params_kernel(self._h, self._ENV_PARAMS_KERNELS[kernel]))
+                self._env_params_kernel = kernel
             _check(self._L.ffm_engine_set_env_params(self._h, None, 0, None, _stream_handle(stream)))
             return
         base = {"k_S": self.params["k_S"], "k_D": self.params["k_D"], "diffuse": self.params["diffuse"],
@@ -411,7 +423,18 @@ class Engine:
             soe = np.ascontiguousarray(set_of_env, dtype=np.int32).reshape(-1)
             if soe.size != self.n_envs:
                 raise ValueError(f"set_of_env must have n_envs = {self.n_envs} entries, got {soe.size}")
-        _check(self._L.ffm_engine_set_env_params(self._h, arr, len(sets), _ptr(soe), _stream_handle(stream)))
+        # the kernel first (a refusal leaves everything as it was); bad tables then put it back
+        before = getattr(self, "_env_params_kernel", "lane")
+        if kernel is not None:
+            _check(self._L.ffm_engine_set_env_params_kernel(self._h, self._ENV_PARAMS_KERNELS[kernel]))
+        try:
+            _check(self._L.ffm_engine_set_env_params(self._h, arr, len(sets), _ptr(soe), _stream_handle(stream)))
+        except Exception:
+            if kernel is not None:
+                self._L.ffm_engine_set_env_params_kernel(self._h, self._ENV_PARAMS_KERNELS[before])
+            raise
+        if kernel is not None:
+            self._env_params_kernel = kernel
 
     def env_params(self):
         """(sets, set_of_env) in effect (ffm_engine_get_env_params): a list of dicts and an int32

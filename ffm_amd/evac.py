@@ -21,6 +21,10 @@ episodes.  ``steps_per_episode.csv`` then carries each env's own N and gains the
 ``sweep_summary.csv`` has one row per set: parameters, count, mean, std, min, max.
 
     python -m ffm_amd.evac --room 12 12 --sweep N=5,10,20,32 --sweep k_D=0,1,4 --envs 4096 --out runs/sweep
+
+``--sweep-kernel {lane,group}`` picks the kernel that steps a sweep in a 12x12 engine (one born on
+the group kernel): the lane kernel's per-env form or the group kernel's own.  The outputs are
+the same bits either way; the default (SWEEP_KERNEL_DEFAULT) is the one that measured faster.
 """
 from __future__ import annotations
 
@@ -33,6 +37,11 @@ import numpy as np
 
 
 SWEEP_NAMES = ("k_S", "k_D", "diffuse", "decay", "N")
+# The kernel of a sweep in an engine born on the group kernel when --sweep-kernel is not given
+# (every other engine has the one choice): the group kernel's own per-env form, which measured
+# faster than the lane kernel's in every run at 4,096, 32,768 and 65,536 envs (1.36, 1.64 and 1.66
+# times; profiles/env_params_group/ab.txt).
+SWEEP_KERNEL_DEFAULT = "group"
 
 
 def parse_sweep(text: str):
@@ -125,7 +134,7 @@ def summary_text(steps: np.ndarray, total_steps: int, seconds: float) -> str:
             f"steps_per_second {rate:.1f}\n")
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--map", help=".npy map (0 free, 2 wall, 3 exit)")
     ap.add_argument("--sff", help=".npy static floor field of the map")
@@ -142,7 +151,16 @@ def main(argv=None):
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--sweep", action="append", default=[], metavar="NAME=v1,v2,...",
                     help="sweep k_S, k_D, diffuse, decay or N in one engine (repeatable: Cartesian product)")
+    ap.add_argument("--sweep-kernel", choices=("lane", "group"), default=None,
+                    help="the kernel that steps a sweep in an engine born on the group kernel (12x12): the lane "
+                         f"kernel's per-env form or the group kernel's own (default: {SWEEP_KERNEL_DEFAULT}; "
+                         "same outputs either way)")
     ap.add_argument("--out", required=True, metavar="DIR")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
     if bool(a.map) != bool(a.sff) or bool(a.map) == bool(a.room):
         ap.error("give either --map and --sff, or --room H W")
@@ -167,8 +185,15 @@ def main(argv=None):
     eng = Engine(m, sff, n_envs=a.envs, n_agents=n_max, params=params, rng="philox", seed=a.seed,
                  auto_reset=a.episodes > 1)
     if sets:   # before the reset: its placement takes each env's own N
-        eng.set_env_params([{"k_S": st["k_S"], "k_D": st["k_D"], "diffuse": st["diffuse"], "decay": st["decay"],
-                             "n_agents": st["N"]} for st in sets], soe)
+        kernel = a.sweep_kernel
+        if kernel is None and eng.launch_info()["kernel"] == "group":
+            kernel = SWEEP_KERNEL_DEFAULT
+        try:
+            eng.set_env_params([{"k_S": st["k_S"], "k_D": st["k_D"], "diffuse": st["diffuse"], "decay": st["decay"],
+                                 "n_agents": st["N"]} for st in sets], soe, kernel=kernel)
+        except NotImplementedError as err:   # --sweep-kernel group on an engine of another kernel
+            eng.close()
+            ap.error(str(err))
     eng.set_episode_log(hist_bins=0)
     eng.reset()
     t0 = time.perf_counter()

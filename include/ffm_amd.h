@@ -258,11 +258,13 @@ int ffm_engine_get_episode_stats(ffm_engine* eng, uint64_t* hist, int32_t bins, 
  * finite parameters, set_of_env entries in [0, n_sets), non-null tables: FFM_E_INVALID.
  * MT engines: FFM_E_UNSUPPORTED.
  *
- * Kernels: the group kernel (12x12 default) and the wave kernel have no per-env form yet.
- * While the feature is on, a group engine steps with the lane kernel and a wave engine with
- * the block kernel (step shards, which belong to the group kernel, are off); both return to
- * their own kernel at n_sets = 0.  Lane, fused and block engines keep theirs.  (A block
- * engine whose LDS has no 32 bytes per env of its workgroup left: FFM_E_UNSUPPORTED.) */
+ * Kernels: the wave kernel has no per-env form.  While the feature is on, a wave engine steps
+ * with the block kernel, and a group engine (12x12 default) by default with the lane kernel
+ * (step shards, which belong to the group kernel, are then off); both return to their own
+ * kernel at n_sets = 0.  ffm_engine_set_env_params_kernel(eng, 1) keeps a group engine on the
+ * group kernel's own per-env form instead, step shards included.  Lane, fused and block
+ * engines keep their kernel.  (A block engine whose LDS has no 32 bytes per env of its
+ * workgroup left: FFM_E_UNSUPPORTED.) */
 typedef struct {
     double k_S, k_D, diffuse, decay;
     int32_t n_agents;
@@ -274,6 +276,12 @@ int ffm_engine_set_env_params(ffm_engine* eng, const ffm_env_params* sets, int32
  * may be NULL; cap < *n_sets: FFM_E_INVALID with *n_sets = count needed. */
 int ffm_engine_get_env_params(ffm_engine* eng, ffm_env_params* sets, int32_t cap, int32_t* n_sets,
                               int32_t* set_of_env /* host [n_envs] or NULL */);
+/* Which kernel steps a group engine while per-env parameters are on.
+ * 0 (default): the lane kernel's per-env form, as before.  1: the group kernel's own per-env
+ * form, with step shards.  Sticky; may be called with the feature on or off, between steps.
+ * An engine not created on the group kernel, or an MT engine, with mode 1: FFM_E_UNSUPPORTED,
+ * nothing changes.  Other modes: FFM_E_INVALID. */
+int ffm_engine_set_env_params_kernel(ffm_engine* eng, int32_t mode);
 
 /* counters[4] = {agent_steps, exits, resets, steps} accumulated since create. */
 int ffm_engine_get_counters(ffm_engine* eng, uint64_t* counters, void* stream);
