@@ -58,7 +58,7 @@ namespace ffm {
 namespace {
 
 struct LaneCarve {
-    size_t grid, tile, words, keys, pend, per_wave;
+    size_t grid, tile, words, keys, pend, sff, per_wave;
 };
 
 // Per-wave LDS: two grids, two tiles, the 64 lanes' friction words, the placement
@@ -68,20 +68,24 @@ struct LaneCarve {
 // i-th pair; the host keeps every wave at <= kLaneMaxPairs pairs.
 constexpr int kLaneMaxPairs = 64;
 constexpr int kLanePendWords = 2 * kLaneMaxPairs / 32;
-__host__ __device__ inline LaneCarve lane_carve(int PHW, int TS, int F) {
+// room (per-env rooms, the ROOM form): each half-wave's grid starts on a 16-byte boundary (stride
+// room_layout().gs codes) and the wave also holds its two envs' SFF (stride ss floats); F is the
+// largest room's.  That form has no block-shared region.
+__host__ __device__ inline LaneCarve lane_carve(int PHW, int TS, int F, bool room = false) {
     LaneCarve c;
     size_t o = 0;
-    c.grid = o;  o += a16((size_t)(2 * PHW) * 2);
+    c.grid = o;  o += a16((size_t)(2 * (room ? room_layout(PHW, F).gs : PHW)) * 2);
     c.tile = o;  o += a16((size_t)(2 * TS) * 4);
     c.words = o; o += 64 * 8;
     c.keys = o;  o += a16((size_t)(F > 0 ? F : 1) * 8);
     c.pend = o;  o += kLanePendWords * 4;
+    c.sff = o;   o += room ? (size_t)(2 * room_layout(PHW, F).ss) * 4 : 0;
     c.per_wave = o;
     return c;
 }
 
-__host__ __device__ inline size_t lane_shared_bytes(int PHW, int F) {
-    return a16((size_t)PHW) + a16((size_t)PHW * 4) + a16((size_t)(F > 0 ? F : 1) * 2);
+__host__ __device__ inline size_t lane_shared_bytes(int PHW, int F, bool room = false) {
+    return room ? 0 : a16((size_t)PHW) + a16((size_t)PHW * 4) + a16((size_t)(F > 0 ? F : 1) * 2);
 }
 
 }  // namespace
@@ -107,9 +111,19 @@ constexpr int lane_waves() { return (NB == 4 && HT == 12) ? (PEP ? FFM_LANE_PEP_
 // EPL: with the episode log (episode_log.h).  PEP: with per-env parameters (a.envp, kernels.h):
 // the lane's env's record is prefetched with the pair's state; decide takes its kS32 / kD32, the
 // stencil the c0 / c1 of each float4 slot's env, the count store and the placement its N.
-template <int NB, int HT, int WT, bool EPL, bool PEP>
+//
+// ROOM (only with PEP): per-env rooms (a.rooms / a.room_of_env, kernels.h).  There is no block-shared
+// room: each half-wave holds its own env's grid codes and SFF in the wave's LDS and re-stages both
+// from the room table (16-byte loads, L2-resident) whenever its next env's room index -- prefetched
+// with the pair's state -- differs from the one its LDS holds.  A grid that stays is kept clean by the
+// unmark, which puts back the code the agent's cell held (not 0: an agent that a caller left standing
+// in another room's wall must not open that wall for the envs that follow).  Every index into the
+// grid, the SFF and the tile comes from a position (< H * W) or a validated free-list entry, none from
+// a map code.  The deferred placements take the env's own room's free list and F from the table.
+template <int NB, int HT, int WT, bool EPL, bool PEP, bool ROOM = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(lane_waves<NB, HT, PEP>(), 8)))
 void core_lane_kernel(CoreStepArgs a) {
+    static_assert(PEP || !ROOM, "the room form takes every env's record");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int H = HT ? HT : a.H, W = WT ? WT : a.W;
     const int HW = H * W, PW = W + 2, PHW = (H + 2) * PW;
@@ -119,16 +133,18 @@ void core_lane_kernel(CoreStepArgs a) {
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int sub = lane >> 5, al = lane & 31;
 
-    const LaneCarve cv = lane_carve(PHW, TS, a.F);
+    const LaneCarve cv = lane_carve(PHW, TS, a.F, ROOM);
+    const RoomLayout lay = room_layout(PHW, a.F);
     uint8_t* pmap = smem;
     float* psff = reinterpret_cast<float*>(smem + a16((size_t)PHW));
     uint16_t* pfree = reinterpret_cast<uint16_t*>(smem + a16((size_t)PHW) + a16((size_t)PHW * 4));
-    unsigned char* wbase = smem + lane_shared_bytes(PHW, a.F) + (size_t)wv * cv.per_wave;
+    unsigned char* wbase = smem + lane_shared_bytes(PHW, a.F, ROOM) + (size_t)wv * cv.per_wave;
     uint16_t* grid = reinterpret_cast<uint16_t*>(wbase + cv.grid);
     float* const tile = reinterpret_cast<float*>(wbase + cv.tile);
     uint2* words = reinterpret_cast<uint2*>(wbase + cv.words);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(wbase + cv.keys);
-    uint16_t* gk = grid + sub * PHW;
+    uint16_t* gk = grid + sub * (ROOM ? lay.gs : PHW);
+    if constexpr (ROOM) psff = reinterpret_cast<float*>(wbase + cv.sff) + sub * lay.ss;   // the half's env's SFF
 
     // The lane's two float4 DFF slots: cells 4q..4q+3 of the pair (q = lane, lane + 64).
     int tb0 = -1, tb1 = -1;
@@ -167,6 +183,7 @@ void core_lane_kernel(CoreStepArgs a) {
         int pos, cnt;
         float4 pr;   // PEP: kS32, kD32, c0, c1 of the lane's env
         int N;       // PEP: its N
+        int room;    // ROOM: its room index
     };
     auto load = [&](int gg, LaneState& st) {
         const int e0 = (gg < 0 ? 0 : gg) * 2;
@@ -182,15 +199,19 @@ void core_lane_kernel(CoreStepArgs a) {
             st.pr = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rp, sub * (int)sizeof(EnvParams), 0, 0));
             st.N = (int)__builtin_amdgcn_raw_buffer_load_b32(rp, sub * (int)sizeof(EnvParams) + 24, 0, 0);
         }
+        if constexpr (ROOM)   // a half past the end reads room 0: a valid record, staged and never stepped
+            st.room = (int)__builtin_amdgcn_raw_buffer_load_b32(pair_rsrc(a.room_of_env + e0, nenv * 4), off_cnt, 0, 0);
     };
     LaneState cur;
     load(g < ngroups ? g : -1, cur);
 
-    for (int i = threadIdx.x; i < PHW; i += 256) {
-        pmap[i] = a.pmap[i];
-        psff[i] = reinterpret_cast<const float*>(a.psff)[i];
+    if constexpr (!ROOM) {
+        for (int i = threadIdx.x; i < PHW; i += 256) {
+            pmap[i] = a.pmap[i];
+            psff[i] = reinterpret_cast<const float*>(a.psff)[i];
+        }
+        for (int i = threadIdx.x; i < a.F; i += 256) pfree[i] = a.free_padded[i];
     }
-    for (int i = threadIdx.x; i < a.F; i += 256) pfree[i] = a.free_padded[i];
     for (int i = lane; i < 2 * TS; i += 64) tile[i] = 0.0f;
     __syncthreads();
     // Two dropped stores, so that on every path into the loop head the two youngest
@@ -198,8 +219,10 @@ void core_lane_kernel(CoreStepArgs a) {
     // not for the previous group's DFF stores).
     buf_st4(pair_rsrc(a.dff, 0), kOOB, make_float4(0.f, 0.f, 0.f, 0.f));
     buf_st4(pair_rsrc(a.dff, 0), kOOB, make_float4(0.f, 0.f, 0.f, 0.f));
-    for (int i = lane; i < 2 * PHW; i += 64) grid[i] = pmap[i - (i / PHW) * PHW];
+    if constexpr (!ROOM)
+        for (int i = lane; i < 2 * PHW; i += 64) grid[i] = pmap[i - (i / PHW) * PHW];
     wave_sync();
+    int held = -1;   // ROOM: the room this half's grid and SFF hold (none yet)
 
     unsigned c_steps = 0, c_exits = 0, c_resets = 0;
     const uint32_t mW = (uint32_t)(((1ull << 32) + (unsigned)W - 1) / (unsigned)W);   // x = c / W for c < 2^16
@@ -227,6 +250,21 @@ void core_lane_kernel(CoreStepArgs a) {
         const uint32_t genv = ebase + (uint32_t)(e0 + sub);
         const float kS32 = PEP ? cur.pr.x : a.kS32, kD32 = PEP ? cur.pr.y : a.kD32;
 
+        // ---- ROOM: this half's env's room, if its LDS holds another ------------------------
+        if constexpr (ROOM) {
+            if (cur.room != held) {   // uniform over the half
+                held = cur.room;
+                // record `held` of the table (the host checked every index); the loops stay inside
+                // the record's grid and SFF parts and the half's LDS strides by construction
+                const unsigned char* rec = a.rooms + (size_t)held * (size_t)a.room_stride;
+                const uint4* gsrc = reinterpret_cast<const uint4*>(rec + lay.grid);
+                const float4* ssrc = reinterpret_cast<const float4*>(rec + lay.sff);
+                for (int q = al; q < lay.gs / 8; q += 32) reinterpret_cast<uint4*>(gk)[q] = gsrc[q];
+                for (int q = al; q < lay.ss / 4; q += 32) reinterpret_cast<float4*>(psff)[q] = ssrc[q];
+            }
+            wave_sync();
+        }
+
         // ---- agent cell and occupancy mark ----------------------------------------------
         const bool live = env_ok && al < cnt;
         const int x = (int)__umulhi(cpos, mW);   // exact for cpos < 2^16
@@ -234,6 +272,7 @@ void core_lane_kernel(CoreStepArgs a) {
         const int pp = live ? (x + 1) * PW + y + 1 : PW + 1;       // idle lanes: an in-bounds cell
         const int dd0 = 3 - (x + 1) * 2;                           // tile index = grid index + dd0 - 2/row
         uint16_t* const mine = gk + pp;
+        const uint16_t under = ROOM ? *mine : (uint16_t)0;         // what the unmark puts back
         if (live) *mine = (uint16_t)(DirCodes::kAgent | (uint32_t)al | (DirCodes::kNoDir << 8));
         {
             const int c0 = __builtin_amdgcn_readlane(cnt, 0), c1 = __builtin_amdgcn_readlane(cnt, 32);
@@ -309,7 +348,7 @@ void core_lane_kernel(CoreStepArgs a) {
             const int c0 = __builtin_amdgcn_readlane(cnt, 0), c1 = __builtin_amdgcn_readlane(cnt, 32);
             c_exits += (unsigned)((c0 - n0) + (nenv > 1 ? c1 - n1 : 0));
         }
-        if (live) *mine = 0;   // unmark: agents only ever stand on free cells
+        if (live) *mine = under;   // unmark: agents only ever stand on free cells (ROOM: see above)
         const bool rs = a.auto_reset && env_ok && newcnt == 0;
         const unsigned long long rsm = __ballot(rs);
         c_resets += (unsigned)(((rsm & 1ull) ? 1 : 0) + ((rsm >> 32) & 1ull ? 1 : 0));
@@ -411,7 +450,12 @@ void core_lane_kernel(CoreStepArgs a) {
             m &= m - 1u;
             const int e = (g_first + (bit >> 1) * wstride) * 2 + (bit & 1);
             if (FFM_LANE_ABLATE & 64) continue;
-            if constexpr (PEP)   // the env's own N and threshold, read here: rare, nothing of the step is live
+            if constexpr (ROOM) {   // ... and its own room's free list and F, from the table
+                const unsigned char* rec = a.rooms + (size_t)a.room_of_env[e] * (size_t)a.room_stride;
+                wave_reset_env(a, ebase + (uint32_t)e, keys, reinterpret_cast<const uint16_t*>(rec + lay.free),
+                               a.pos + (long long)e * A, lane, a.envp[e].N, a.envp[e].reset_thr,
+                               min(*reinterpret_cast<const int*>(rec), a.F));   // keys holds a.F pairs
+            } else if constexpr (PEP)   // the env's own N and threshold, read here: rare, nothing of the step is live
                 wave_reset_env(a, ebase + (uint32_t)e, keys, pfree, a.pos + (long long)e * A, lane, a.envp[e].N,
                                a.envp[e].reset_thr);
             else wave_reset_env(a, ebase + (uint32_t)e, keys, pfree, a.pos + (long long)e * A, lane);
@@ -433,19 +477,23 @@ void core_lane_kernel(CoreStepArgs a) {
     }
 }
 
-size_t core_lane_smem_bytes(int H, int W, int F, int waves) {
+size_t core_lane_smem_bytes(int H, int W, int F, int waves, bool room) {
     const int PHW = (H + 2) * (W + 2);
-    return lane_shared_bytes(PHW, F) + (size_t)waves * lane_carve(PHW, lane_tile_floats(H, W), F).per_wave;
+    return lane_shared_bytes(PHW, F, room) + (size_t)waves * lane_carve(PHW, lane_tile_floats(H, W), F, room).per_wave;
 }
 
 template <int NB, int HT, int WT>
 static hipError_t lane_op(const CoreStepArgs& a, int blocks, hipStream_t s, int op, int* occ) {
-    const size_t smem = core_lane_smem_bytes(a.H, a.W, a.F, 4);
+    const bool room = a.rooms != nullptr;   // per-env rooms: with the records (envp), or not at all
+    if (room && (!a.envp || !a.room_of_env)) return hipErrorInvalidValue;
+    const size_t smem = core_lane_smem_bytes(a.H, a.W, a.F, 4, room);
     if (!op && ((a.E + 1) / 2 + (long long)blocks * 4 - 1) / ((long long)blocks * 4) > kLaneMaxPairs)
         return hipErrorInvalidConfiguration;   // the grid must give every wave <= kLaneMaxPairs pairs
     if (op) {
         *occ = 0;
-        const hipError_t he = a.envp ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        const hipError_t he = room   ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                                           occ, core_lane_kernel<NB, HT, WT, false, true, true>, 256, smem)
+                              : a.envp ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
                                            occ, core_lane_kernel<NB, HT, WT, false, true>, 256, smem)
                                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(
                                            occ, core_lane_kernel<NB, HT, WT, false, false>, 256, smem);
@@ -453,7 +501,10 @@ static hipError_t lane_op(const CoreStepArgs& a, int blocks, hipStream_t s, int 
         return hipSuccess;
     }
     const dim3 gd((unsigned)blocks), bd(256);
-    if (a.envp) {   // per-env parameters
+    if (room) {   // per-env rooms
+        if (a.ep_start) core_lane_kernel<NB, HT, WT, true, true, true><<<gd, bd, smem, s>>>(a);
+        else core_lane_kernel<NB, HT, WT, false, true, true><<<gd, bd, smem, s>>>(a);
+    } else if (a.envp) {   // per-env parameters
         if (a.ep_start) core_lane_kernel<NB, HT, WT, true, true><<<gd, bd, smem, s>>>(a);
         else core_lane_kernel<NB, HT, WT, false, true><<<gd, bd, smem, s>>>(a);
     } else if (a.ep_start) core_lane_kernel<NB, HT, WT, true, false><<<gd, bd, smem, s>>>(a);

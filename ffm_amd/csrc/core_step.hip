@@ -1098,8 +1098,11 @@ void core_block_kernel(CoreStepArgs a) {
 // re-placed, their DFF row zeroed and their position row cleared here (the whole-engine reset
 // clears every row by memset beforehand).
 // PEP: the env's own N and candidate threshold (per-env parameters, a.envp).
-template <bool PEP>
+// ROOM (with PEP): the free list and F of the env's own room, from the room table (per-env rooms,
+// kernels.h); a.F is the largest room's, which sizes the LDS.
+template <bool PEP, bool ROOM = false>
 __global__ __launch_bounds__(64) void core_reset_kernel(CoreStepArgs a, const uint8_t* mask) {
+    static_assert(PEP || !ROOM, "the room form takes every env's record");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);
     uint16_t* fl = reinterpret_cast<uint16_t*>(smem + align16((size_t)a.F * 8));
@@ -1109,11 +1112,18 @@ __global__ __launch_bounds__(64) void core_reset_kernel(CoreStepArgs a, const ui
         for (int i = threadIdx.x; i < a.HW; i += 64) a.dff[e * a.HW + i] = 0.0f;
         for (int i = threadIdx.x; i < a.A; i += 64) a.pos[e * a.A + i] = 0xFFFFu;
     }
-    for (int i = threadIdx.x; i < a.F; i += 64) fl[i] = a.free_padded[i];
+    int F = a.F;
+    const uint16_t* src = a.free_padded;
+    if constexpr (ROOM) {
+        const unsigned char* rec = a.rooms + (size_t)a.room_of_env[e] * (size_t)a.room_stride;
+        F = min(*reinterpret_cast<const int*>(rec), a.F);   // the LDS holds a.F entries
+        src = reinterpret_cast<const uint16_t*>(rec + room_layout((a.H + 2) * (a.W + 2), a.F).free);
+    }
+    for (int i = threadIdx.x; i < F; i += 64) fl[i] = src[i];
     wave_sync();
     const int N = PEP ? a.envp[e].N : a.N;
     wave_reset_env(a, (uint32_t)(a.env_base + e), keys, fl, a.pos + e * a.A, threadIdx.x, N,
-                   PEP ? a.envp[e].reset_thr : a.reset_thr);
+                   PEP ? a.envp[e].reset_thr : a.reset_thr, F);
     if (threadIdx.x == 0) {
         a.cnt[e] = N;
         eplog_mark_start(a, e, a.t);
@@ -1291,7 +1301,8 @@ hipError_t launch_core_block_reset(const CoreStepArgs& a, hipStream_t s, const u
 hipError_t launch_core_reset(const CoreStepArgs& a, hipStream_t s, const uint8_t* mask) {
     const size_t smem = align16((size_t)(a.F > 0 ? a.F : 1) * 8) + align16((size_t)(a.N > 0 ? a.N : 1) * 2) +
                         align16((size_t)(a.F > 0 ? a.F : 1) * 2);
-    if (a.envp) core_reset_kernel<true><<<dim3((unsigned)a.E), dim3(64), smem, s>>>(a, mask);
+    if (a.rooms) core_reset_kernel<true, true><<<dim3((unsigned)a.E), dim3(64), smem, s>>>(a, mask);
+    else if (a.envp) core_reset_kernel<true><<<dim3((unsigned)a.E), dim3(64), smem, s>>>(a, mask);
     else core_reset_kernel<false><<<dim3((unsigned)a.E), dim3(64), smem, s>>>(a, mask);
     return hipGetLastError();
 }

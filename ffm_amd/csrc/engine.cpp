@@ -120,18 +120,39 @@ struct ffm_engine {
     std::vector<Shard> pep_shards;             // ... and its step shards (size() <= 1: off)
     unsigned char* d_stage_raw = nullptr;      // its stage image: the SFF term with multiplier 1 (the raw SFF);
                                                // built when the feature first moves to the group kernel
+    // Per-env rooms (ffm_engine_set_env_rooms): null / empty while off.  While on the engine steps
+    // with the lane kernel's room form and d_envp holds a record per env: the caller's sets', or
+    // (pep_sets empty) the create-time values, each with its room's placement threshold.
+    bool lane_ok = false;                      // the lane kernel's conditions hold (create)
+    unsigned char* d_rooms = nullptr;          // the room table (kernels.h room_layout)
+    int32_t* d_room_of_env = nullptr;          // [n_envs]
+    size_t room_stride = 0;
+    int room_fmax = 0;                         // the largest room's free-cell count
+    int room_lane_blocks = 0;                  // the room form's persistent grid
+    std::vector<uint8_t> room_maps;            // the caller's tables, for ffm_engine_get_env_rooms
+    std::vector<float> room_sffs;
+    std::vector<int32_t> room_of_env;
+    std::vector<int> room_f;                   // free cells of every room
 };
+
+static bool rooms_on(const ffm_engine* e) { return e->d_rooms != nullptr; }
+// Per-env parameters as the caller set them (the records of an engine with rooms only are the engine's own).
+static bool pep_on(const ffm_engine* e) { return e->d_envp && !e->pep_sets.empty(); }
 
 // The kernel that steps the engine under its current settings (per-env parameters move group and
 // wave engines): at most one of these holds, none means the block kernel.
-static bool pep_group_on(const ffm_engine* e) { return e->d_envp && e->pep_group; }
-static bool steps_group(const ffm_engine* e) { return e->group && (!e->d_envp || e->pep_group); }
-static bool steps_lane(const ffm_engine* e) { return e->d_envp ? e->pep_lane && !e->pep_group : e->lane; }
+static bool pep_group_on(const ffm_engine* e) { return !rooms_on(e) && e->d_envp && e->pep_group; }
+static bool steps_group(const ffm_engine* e) { return !rooms_on(e) && e->group && (!e->d_envp || e->pep_group); }
+static bool steps_lane(const ffm_engine* e) {
+    return rooms_on(e) || (e->d_envp ? e->pep_lane && !e->pep_group : e->lane);
+}
 static bool steps_wave(const ffm_engine* e) { return e->wave && !e->d_envp; }
 // Blocks per CU of the group kernel's largest grid (engine create, group_grid).
 constexpr int kGroupGridPerCu = 8;
 
-static int lane_blocks_now(const ffm_engine* e) { return e->d_envp ? e->pep_lane_blocks : e->lane_blocks; }
+static int lane_blocks_now(const ffm_engine* e) {
+    return rooms_on(e) ? e->room_lane_blocks : e->d_envp ? e->pep_lane_blocks : e->lane_blocks;
+}
 // The group kernel's launch geometry in effect: the create-time one, or the per-env form's.
 static int group_blocks_now(const ffm_engine* e) { return pep_group_on(e) ? e->pep_group_blocks : e->group_blocks; }
 static int group_g_now(const ffm_engine* e) { return pep_group_on(e) ? e->pep_group_g : e->group_g; }
@@ -305,6 +326,8 @@ static void release(ffm_engine* e) {
     (void)hipFree(e->d_dbg);
     (void)hipFree(e->d_scratch);
     (void)hipFree(e->d_envp);
+    (void)hipFree(e->d_rooms);
+    (void)hipFree(e->d_room_of_env);
     free_capture(e);
     free_episode_log(e, true);
     delete e;
@@ -391,6 +414,7 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
     // -1 = wave kernel, -2 = lane kernel, -3 = group kernel.
     const bool lane_ok = !e->mt && !e->f64 && A <= 32 && W % 4 == 0 && HW <= 256 &&
                          ((long long)d.n_envs + 7) * HW * 4 < (1ll << 31);   // 32-bit buffer offsets (padded envs)
+    e->lane_ok = lane_ok;
     e->group = (d.envs_per_block == 0 || d.envs_per_block == -3) && lane_ok && ffm::core_group_supported(H, W) &&
                ffm::core_group_smem_bytes(H, W, e->F, 4) <= 64 * 1024;
     e->multi = lane_ok && ffm::core_multi_smem_bytes(H, W, e->F, 4) <= 64 * 1024;
@@ -593,7 +617,7 @@ static ffm::CoreStepArgs make_args(ffm_engine* e) {
     a.N = e->d.n_agents;
     a.free_list = e->d_free;
     a.free_padded = e->d_free_padded;
-    a.F = e->F;
+    a.F = rooms_on(e) ? e->room_fmax : e->F;   // per-env rooms: the largest room's (the LDS sizes)
     a.reset_thr = e->reset_thr;
     a.stage = pep_group_on(e) ? e->d_stage_raw : e->d_stage;   // the per-env form takes k_S from the records
     a.stage_q4 = e->stage_q4;
@@ -610,6 +634,9 @@ static ffm::CoreStepArgs make_args(ffm_engine* e) {
     a.ephist_bins = e->ephist_bins;
     a.epsum = e->d_ephist ? e->d_ephist + ep_sum_offset(e->ephist_bins) : nullptr;
     a.envp = e->d_envp;
+    a.rooms = e->d_rooms;
+    a.room_of_env = e->d_room_of_env;
+    a.room_stride = (int)e->room_stride;
     return a;
 }
 
@@ -619,7 +646,7 @@ static ffm::CoreStepArgs make_args(ffm_engine* e) {
 // (the shards belong to the group kernel; on its per-env form they are that form's own).
 static int shards_in_effect(const ffm_engine* e) {
     const std::vector<ffm_engine::Shard>& sh = shards_now(e);
-    if (sh.size() <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi) || !steps_group(e)) return 1;
+    if (sh.size() <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi && !rooms_on(e)) || !steps_group(e)) return 1;
     return (int)sh.size();
 }
 
@@ -672,7 +699,7 @@ static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
 int ffm_engine_step(ffm_engine* e, int32_t n_steps, void* stream) {
     if (!e || n_steps < 0) return fail(FFM_E_INVALID, "bad engine/n_steps");
     hipStream_t s = (hipStream_t)stream;
-    if (e->fused > 1 && e->multi && e->cap.n_sel == 0) {
+    if (e->fused > 1 && e->multi && e->cap.n_sel == 0 && !rooms_on(e)) {
         // k steps per launch, the state of each env pair on chip (core_multi.hip)
         for (int done = 0; done < n_steps;) {
             const int k = std::min(e->fused, n_steps - done);
@@ -797,7 +824,9 @@ int ffm_engine_set_state(ffm_engine* e, int64_t env0, int64_t n, const uint16_t*
         for (int64_t i = 0; i < n; i++) {
             for (int j = 0; j < counts[i]; j++) {
                 const uint16_t c = positions[i * A + j];
-                if (c >= e->HW || pmap[(c / e->d.W + 1) * PW + c % e->d.W + 1] != 0)
+                // per-env rooms: the env's own room's map
+                if (c >= e->HW || (rooms_on(e) ? e->room_maps[(size_t)e->room_of_env[(size_t)(env0 + i)] * e->HW + c]
+                                               : pmap[(c / e->d.W + 1) * PW + c % e->d.W + 1]) != 0)
                     return fail(FFM_E_INVALID, "agent on a non-free cell");
                 if (seen[c]) return fail(FFM_E_INVALID, "two agents on one cell");
                 seen[c] = 1;
@@ -1018,6 +1047,54 @@ int ffm_engine_get_episode_stats(ffm_engine* e, uint64_t* hist, int32_t bins, ui
     return FFM_OK;
 }
 
+// One env's record (kernels.h EnvParams) from its parameter set, with the expressions of
+// ffm_engine_create (the same bits as a homogeneous engine).  F: the free cells of the env's room.
+static ffm::EnvParams env_record(const ffm_env_params& q, int nb, int F) {
+    ffm::EnvParams r{};
+    r.kS32 = (float)(-q.k_S);
+    r.kD32 = (float)q.k_D;
+    r.kS64 = -q.k_S;
+    r.c0 = (float)((1.0 - q.decay) * (1.0 - q.diffuse));
+    r.c1 = (float)(q.decay * (1.0 - q.diffuse) / (double)nb);
+    r.N = q.n_agents;
+    const int N = q.n_agents;
+    int M = std::min(F, N + std::max(8, (N + 1) / 2));
+    if (const char* ov = std::getenv("FFM_RESET_CANDIDATES")) M = std::max(0, std::min(F, std::atoi(ov)));
+    r.reset_thr = M == 0 ? 0u : M == F ? 0xFFFFFFFFu : (uint32_t)(((uint64_t)M << 32) / (uint64_t)F);
+    return r;
+}
+
+// The create-time parameters as a set (the records of an engine with rooms but no sets).
+static ffm_env_params create_set(const ffm_engine* e) {
+    ffm_env_params q{};
+    q.k_S = e->d.k_S; q.k_D = e->d.k_D; q.diffuse = e->d.diffuse; q.decay = e->d.decay;
+    q.n_agents = e->d.n_agents;
+    return q;
+}
+
+// Every env's record.  sets == nullptr: the create-time set for every env.  room_f == nullptr: the
+// create-time room's F for every env, else room_f[room_of_env[i]].
+static std::vector<ffm::EnvParams> env_records(const ffm_engine* e, const ffm_env_params* sets, const int32_t* set_of_env,
+                                               const std::vector<int>* room_f, const int32_t* room_of_env) {
+    const size_t E = (size_t)e->d.n_envs;
+    const ffm_env_params base = create_set(e);
+    std::vector<ffm::EnvParams> rec(E);
+    for (size_t i = 0; i < E; i++)
+        rec[i] = env_record(sets ? sets[set_of_env[i]] : base, e->d.neighborhood,
+                            room_f ? (*room_f)[(size_t)room_of_env[i]] : e->F);
+    return rec;
+}
+
+// The first env whose n_agents exceeds the free cells of its room, or -1 (same arguments).
+static long long env_over_capacity(const ffm_engine* e, const ffm_env_params* sets, const int32_t* set_of_env,
+                                   const std::vector<int>* room_f, const int32_t* room_of_env) {
+    for (long long i = 0; i < e->d.n_envs; i++) {
+        const int N = sets ? sets[set_of_env[i]].n_agents : e->d.n_agents;
+        if (N > (room_f ? (*room_f)[(size_t)room_of_env[i]] : e->F)) return i;
+    }
+    return -1;
+}
+
 // What the group kernel's per-env form needs beyond the records: its stage image (built once:
 // the create-time image with the SFF term's multiplier 1, so the LDS region holds the raw SFF) and
 // its launch geometry, sized from that form's occupancy (envp: any non-null pointer, it only
@@ -1070,12 +1147,12 @@ int ffm_engine_set_env_params_kernel(ffm_engine* e, int32_t mode) {
     if (mode != 0 && mode != 1) return fail(FFM_E_INVALID, "env params kernel: mode must be 0 (lane) or 1 (group)");
     if (mode == 1 && (!e->group || e->mt))
         return fail(FFM_E_UNSUPPORTED, "env params kernel: the engine was not created on the group kernel");
-    if (mode == 1 && e->d_envp && !e->pep_group) {   // the feature is on: move it now
+    if (mode == 1 && pep_on(e) && !e->pep_group) {   // the feature is on: move it now
         const int rc = pep_group_setup(e, e->d_envp);
         if (rc) return rc;
     }
     e->pep_kernel = mode;
-    e->pep_group = mode == 1 && e->d_envp != nullptr;
+    e->pep_group = mode == 1 && pep_on(e);
     return FFM_OK;
 }
 
@@ -1086,10 +1163,19 @@ int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t
     if (n_sets < 0 || n_sets > e->d.n_envs) return fail(FFM_E_INVALID, "env params: n_sets must lie in [0, n_envs]");
     hipStream_t s = (hipStream_t)stream;
     if (n_sets == 0) {   // off: the create-time parameters, kernel and launch geometry
-        if (!e->d_envp) return FFM_OK;
-        HIP_TRY(hipStreamSynchronize(s));        // queued steps may still read the records
-        (void)hipFree(e->d_envp);
-        e->d_envp = nullptr;
+        if (!pep_on(e)) return FFM_OK;
+        if (rooms_on(e)) {   // the rooms keep a record per env: the create-time values, each room's threshold
+            if (env_over_capacity(e, nullptr, nullptr, &e->room_f, e->room_of_env.data()) >= 0)
+                return fail(FFM_E_INVALID, "env params: the create-time n_agents exceeds the free cells of an env's room");
+            const std::vector<ffm::EnvParams> rec = env_records(e, nullptr, nullptr, &e->room_f, e->room_of_env.data());
+            HIP_TRY(hipStreamSynchronize(s));
+            HIP_TRY(hipMemcpyAsync(e->d_envp, rec.data(), rec.size() * sizeof(ffm::EnvParams), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        } else {
+            HIP_TRY(hipStreamSynchronize(s));        // queued steps may still read the records
+            (void)hipFree(e->d_envp);
+            e->d_envp = nullptr;
+        }
         e->pep_sets.clear();
         e->pep_set_of_env.clear();
         e->pep_lane = false;
@@ -1104,12 +1190,16 @@ int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t
         const ffm_env_params& q = sets[p];
         if (!std::isfinite(q.k_S) || !std::isfinite(q.k_D) || !std::isfinite(q.diffuse) || !std::isfinite(q.decay))
             return fail(FFM_E_INVALID, "env params: non-finite parameter");
-        if (q.n_agents < 1 || q.n_agents > std::min(A, e->F))
+        if (q.n_agents < 1 || q.n_agents > std::min(A, rooms_on(e) ? e->room_fmax : e->F))
             return fail(FFM_E_INVALID, "env params: n_agents must lie in [1, min(agent_capacity, free cells)]");
     }
     const size_t E = (size_t)e->d.n_envs;
     for (size_t i = 0; i < E; i++)
         if (set_of_env[i] < 0 || set_of_env[i] >= n_sets) return fail(FFM_E_INVALID, "env params: set_of_env out of range");
+    // per-env rooms: every env's n_agents against the free cells of its own room
+    const std::vector<int>* room_f = rooms_on(e) ? &e->room_f : nullptr;
+    if (room_f && env_over_capacity(e, sets, set_of_env, room_f, e->room_of_env.data()) >= 0)
+        return fail(FFM_E_INVALID, "env params: n_agents exceeds the free cells of an env's room");
     // The kernel while on.  Group engines: the lane kernel (the group kernel's conditions include
     // the lane kernel's); wave engines, and whatever else is not on the lane kernel: the block kernel.
     const bool lane = e->lane || (e->group && ffm::core_lane_smem_bytes(e->d.H, e->d.W, e->F, 4) <= 64 * 1024);
@@ -1118,25 +1208,10 @@ int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t
                 ffm::core_block_pep_smem_bytes(e->K) > 64 * 1024)
         return fail(FFM_E_UNSUPPORTED, "env params: the block kernel's LDS has no room for the K records");
     // The records, with the expressions of ffm_engine_create (the same bits as a homogeneous engine)
-    std::vector<ffm::EnvParams> rec(E);
-    const char* ov = std::getenv("FFM_RESET_CANDIDATES");
-    for (size_t i = 0; i < E; i++) {
-        const ffm_env_params& q = sets[set_of_env[i]];
-        ffm::EnvParams& r = rec[i];
-        r.kS32 = (float)(-q.k_S);
-        r.kD32 = (float)q.k_D;
-        r.kS64 = -q.k_S;
-        r.c0 = (float)((1.0 - q.decay) * (1.0 - q.diffuse));
-        r.c1 = (float)(q.decay * (1.0 - q.diffuse) / (double)nb);
-        r.N = q.n_agents;
-        const int N = q.n_agents, F = e->F;
-        int M = std::min(F, N + std::max(8, (N + 1) / 2));
-        if (ov) M = std::max(0, std::min(F, std::atoi(ov)));
-        r.reset_thr = M == 0 ? 0u : M == F ? 0xFFFFFFFFu : (uint32_t)(((uint64_t)M << 32) / (uint64_t)F);
-    }
+    const std::vector<ffm::EnvParams> rec = env_records(e, sets, set_of_env, room_f, e->room_of_env.data());
     HIP_TRY(hipSetDevice(e->d.device));
     int lane_blocks = 0;
-    ffm::EnvParams* buf = e->d_envp;
+    ffm::EnvParams* buf = e->d_envp;   // (per-env rooms: the engine's own records are there already)
     if (!buf) {
         hipError_t he = hipMalloc((void**)&buf, E * sizeof(ffm::EnvParams));
         if (he != hipSuccess) return fail(FFM_E_NOMEM, std::string("env params: ") + hipGetErrorString(he));
@@ -1182,6 +1257,158 @@ int ffm_engine_get_env_params(ffm_engine* e, ffm_env_params* sets, int32_t cap, 
         std::copy(e->pep_sets.begin(), e->pep_sets.end(), sets);
     }
     if (set_of_env) std::copy(e->pep_set_of_env.begin(), e->pep_set_of_env.end(), set_of_env);
+    return FFM_OK;
+}
+
+int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sffs, int32_t n_rooms,
+                             const int32_t* room_of_env, void* stream) {
+    if (!e) return fail(FFM_E_INVALID, "null engine");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t E = (size_t)e->d.n_envs;
+    const bool pep = pep_on(e);
+    if (n_rooms == 0) {   // off: the create-time room, kernel and launch geometry
+        if (!rooms_on(e)) return FFM_OK;
+        if (pep) {   // the sets stay: their records with the create-time room's threshold again
+            if (env_over_capacity(e, e->pep_sets.data(), e->pep_set_of_env.data(), nullptr, nullptr) >= 0)
+                return fail(FFM_E_INVALID, "env rooms: a parameter set's n_agents exceeds the create-time room's free cells");
+            const std::vector<ffm::EnvParams> rec =
+                env_records(e, e->pep_sets.data(), e->pep_set_of_env.data(), nullptr, nullptr);
+            HIP_TRY(hipStreamSynchronize(s));        // queued steps may still read the records and tables
+            HIP_TRY(hipMemcpyAsync(e->d_envp, rec.data(), E * sizeof(ffm::EnvParams), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        } else {
+            HIP_TRY(hipStreamSynchronize(s));
+            (void)hipFree(e->d_envp);
+            e->d_envp = nullptr;
+        }
+        (void)hipFree(e->d_rooms);
+        (void)hipFree(e->d_room_of_env);
+        e->d_rooms = nullptr;
+        e->d_room_of_env = nullptr;
+        e->room_stride = 0;
+        e->room_fmax = 0;
+        e->room_lane_blocks = 0;
+        e->room_maps.clear();
+        e->room_sffs.clear();
+        e->room_of_env.clear();
+        e->room_f.clear();
+        return FFM_OK;
+    }
+    if (e->mt) return fail(FFM_E_UNSUPPORTED, "env rooms: Philox engines only");
+    if (e->f64) return fail(FFM_E_UNSUPPORTED, "env rooms: float32-SFF engines only");
+    if (!e->lane_ok)
+        return fail(FFM_E_UNSUPPORTED, "env rooms: engines of the lane kernel's shapes only (agent_capacity <= 32, W % 4 == 0, H*W <= 256)");
+    if (n_rooms < 1 || n_rooms > e->d.n_envs) return fail(FFM_E_INVALID, "env rooms: n_rooms must lie in [0, n_envs]");
+    if (!maps || !sffs || !room_of_env) return fail(FFM_E_INVALID, "env rooms: maps, sffs and room_of_env are required");
+    const int H = e->d.H, W = e->d.W, HW = e->HW, PW = W + 2, PHW = (H + 2) * PW;
+    // every room's free list, with the checks of ffm_engine_create
+    std::vector<std::vector<uint16_t>> fp((size_t)n_rooms);   // padded indices
+    std::vector<int> room_f((size_t)n_rooms);
+    int fmax = 0;
+    for (int32_t r = 0; r < n_rooms; r++) {
+        const uint8_t* m = maps + (size_t)r * HW;
+        for (int i = 0; i < HW; i++) {
+            const int x = i / W, y = i % W;
+            if (m[i] != 0) continue;
+            if (x == 0 || y == 0 || x == H - 1 || y == W - 1)
+                return fail(FFM_E_INVALID, "free cell on the map border (walls must enclose the room)");
+            fp[(size_t)r].push_back((uint16_t)((x + 1) * PW + y + 1));
+        }
+        room_f[(size_t)r] = (int)fp[(size_t)r].size();
+        fmax = std::max(fmax, room_f[(size_t)r]);
+    }
+    for (size_t i = 0; i < E; i++)
+        if (room_of_env[i] < 0 || room_of_env[i] >= n_rooms) return fail(FFM_E_INVALID, "env rooms: room_of_env out of range");
+    if (ffm::core_lane_smem_bytes(H, W, fmax, 4, true) > 64 * 1024)
+        return fail(FFM_E_UNSUPPORTED, "env rooms: the lane kernel's LDS has no room for the largest room");
+    const ffm_env_params* sets = pep ? e->pep_sets.data() : nullptr;
+    const int32_t* set_of_env = pep ? e->pep_set_of_env.data() : nullptr;
+    if (env_over_capacity(e, sets, set_of_env, &room_f, room_of_env) >= 0)
+        return fail(FFM_E_INVALID, "Cannot take a larger sample than population when 'replace=False' (an env's room "
+                                   "has fewer free cells than its n_agents)");
+    // the table (kernels.h room_layout) and the records
+    const ffm::RoomLayout lay = ffm::room_layout(PHW, fmax);
+    std::vector<unsigned char> table((size_t)n_rooms * lay.stride, 0);
+    for (int32_t r = 0; r < n_rooms; r++) {
+        unsigned char* rec = table.data() + (size_t)r * lay.stride;
+        *reinterpret_cast<int32_t*>(rec) = room_f[(size_t)r];
+        uint16_t* g = reinterpret_cast<uint16_t*>(rec + lay.grid);
+        float* sf = reinterpret_cast<float*>(rec + lay.sff);
+        uint16_t* fr = reinterpret_cast<uint16_t*>(rec + lay.free);
+        for (int i = 0; i < lay.gs; i++) g[i] = 2;   // halo and padding: blocked
+        for (int x = 0; x < H; x++)
+            for (int y = 0; y < W; y++) {
+                const int i = x * W + y, p = (x + 1) * PW + y + 1;
+                const uint8_t c = maps[(size_t)r * HW + i];
+                g[p] = c == 0 ? 0 : c == 3 ? 3 : 2;
+                sf[p] = sffs[(size_t)r * HW + i];
+            }
+        // the list's tail up to the largest F: an in-bounds cell, never read (every loop stops at the room's F)
+        for (int j = 0; j < std::max(1, fmax); j++)
+            fr[j] = j < room_f[(size_t)r] ? fp[(size_t)r][(size_t)j] : (uint16_t)(PW + 1);
+    }
+    const std::vector<ffm::EnvParams> rec = env_records(e, sets, set_of_env, &room_f, room_of_env);
+
+    HIP_TRY(hipSetDevice(e->d.device));
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->d.device));
+    unsigned char* d_rooms = nullptr;
+    int32_t* d_roe = nullptr;
+    ffm::EnvParams* d_envp = nullptr;
+    auto undo = [&](int rc) {
+        (void)hipFree(d_rooms);
+        (void)hipFree(d_roe);
+        (void)hipFree(d_envp);
+        return rc;
+    };
+    // room_of_env is read in pairs through buffer resources: whole pairs, zeroed padding
+    const size_t roe_bytes = ((E + 7) & ~(size_t)7) * 4;
+    hipError_t he = hipMalloc((void**)&d_rooms, table.size());
+    if (he == hipSuccess) he = hipMalloc((void**)&d_roe, roe_bytes);
+    if (he == hipSuccess) he = hipMalloc((void**)&d_envp, E * sizeof(ffm::EnvParams));
+    if (he != hipSuccess) return undo(fail(FFM_E_NOMEM, std::string("env rooms: ") + hipGetErrorString(he)));
+    int lane_blocks = 0;
+    {
+        ffm::CoreStepArgs a{};
+        a.H = H; a.W = W; a.A = e->d.agent_capacity; a.F = fmax; a.auto_reset = e->d.auto_reset;
+        a.envp = d_envp; a.rooms = d_rooms; a.room_of_env = d_roe;   // the occupancy of the room form
+        lane_blocks = lane_grid(a, e->d.neighborhood, e->d.n_envs, cus);
+    }
+    if ((size_t)lane_blocks * 4 > e->ctr_slots) return undo(fail(FFM_E_UNSUPPORTED, "env rooms: counter slots"));
+    // stream-ordered after the steps queued so far; the tables are consumed before the return
+    he = hipStreamSynchronize(s);
+    if (he == hipSuccess) he = hipMemsetAsync(d_roe, 0, roe_bytes, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(d_roe, room_of_env, E * 4, hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(d_rooms, table.data(), table.size(), hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(d_envp, rec.data(), E * sizeof(ffm::EnvParams), hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    if (he != hipSuccess) return undo(fail(FFM_E_HIP, std::string("env rooms: ") + hipGetErrorString(he)));
+    (void)hipFree(e->d_rooms);
+    (void)hipFree(e->d_room_of_env);
+    (void)hipFree(e->d_envp);
+    e->d_rooms = d_rooms;
+    e->d_room_of_env = d_roe;
+    e->d_envp = d_envp;
+    e->room_stride = lay.stride;
+    e->room_fmax = fmax;
+    e->room_lane_blocks = lane_blocks;
+    e->room_maps.assign(maps, maps + (size_t)n_rooms * HW);
+    e->room_sffs.assign(sffs, sffs + (size_t)n_rooms * HW);
+    e->room_of_env.assign(room_of_env, room_of_env + E);
+    e->room_f = std::move(room_f);
+    return FFM_OK;
+}
+
+int ffm_engine_get_env_rooms(ffm_engine* e, uint8_t* maps, float* sffs, int32_t cap, int32_t* n_rooms,
+                             int32_t* room_of_env) {
+    if (!e || !n_rooms || cap < 0) return fail(FFM_E_INVALID, "null argument");
+    *n_rooms = (int32_t)e->room_f.size();
+    if (*n_rooms == 0) return FFM_OK;
+    if ((maps || sffs) && cap < *n_rooms)
+        return fail(FFM_E_INVALID, "get_env_rooms: buffer too small (*n_rooms holds the count)");
+    if (maps) std::copy(e->room_maps.begin(), e->room_maps.end(), maps);
+    if (sffs) std::copy(e->room_sffs.begin(), e->room_sffs.end(), sffs);
+    if (room_of_env) std::copy(e->room_of_env.begin(), e->room_of_env.end(), room_of_env);
     return FFM_OK;
 }
 

@@ -80,7 +80,34 @@ struct CoreStepArgs {
     // Per-env parameters: [E] records, or nullptr (off: kS32 .. c1, N and reset_thr above hold for
     // every env).  The launchers pick the kernels' PEP instantiations when it is set.
     const EnvParams* envp;
+    // Per-env rooms (ffm_engine_set_env_rooms): the room table (one record of room_stride bytes per
+    // room, room_layout below) and the [E] room index of every env, or nullptr (off: pmap, psff and
+    // the free lists above hold for every env).  While set, envp is set too, F above is the largest
+    // room's (the LDS sizes) and the launchers pick the lane and reset kernels' ROOM instantiations.
+    const unsigned char* rooms;
+    const int* room_of_env;
+    int room_stride;
 };
+
+// One record of the room table: 16-byte aligned, every part a whole number of 16-byte words so a
+// half-wave stages a room with 16-byte loads.  hdr: F, the room's free-cell count (one int, padded to
+// 16 bytes); grid: the padded grid-initialisation codes as u16 (0 free, 2 blocked, 3 exit), gs of
+// them; sff: the padded f32 SFF, ss floats; free: the padded free list, room for the largest F.
+struct RoomLayout {
+    int gs, ss;                 // u16 codes / floats per room in the record and in a half-wave's LDS
+    size_t grid, sff, free;     // byte offsets in the record (F at 0)
+    size_t stride;
+};
+__host__ __device__ inline RoomLayout room_layout(int PHW, int Fmax) {
+    RoomLayout r;
+    r.gs = (PHW + 7) & ~7;
+    r.ss = (PHW + 3) & ~3;
+    r.grid = 16;
+    r.sff = r.grid + (size_t)r.gs * 2;
+    r.free = r.sff + (size_t)r.ss * 4;
+    r.stride = (r.free + (size_t)(Fmax > 0 ? Fmax : 1) * 2 + 15) & ~(size_t)15;
+    return r;
+}
 
 // The summary is spread over slots of one 128-byte line each: a single contended word takes
 // about 100 atomic adds per us, and C2 ends about 700 episodes per step.
@@ -103,7 +130,7 @@ size_t core_wave_smem_bytes(int H, int W, int A, int F, bool mt, bool reset, int
 size_t core_block_smem_bytes(int H, int W, int A, int K, int F, bool f64, bool mt, bool reset);
 hipError_t launch_core_wave(const CoreStepArgs& a, int nb, bool mt, int blocks, hipStream_t s);
 int core_wave_blocks_per_cu(const CoreStepArgs& a, int nb, bool mt);
-size_t core_lane_smem_bytes(int H, int W, int F, int waves);
+size_t core_lane_smem_bytes(int H, int W, int F, int waves, bool room = false);   // room: the per-env-rooms form's
 hipError_t launch_core_lane(const CoreStepArgs& a, int nb, int blocks, hipStream_t s);
 int core_lane_blocks_per_cu(const CoreStepArgs& a, int nb);
 int core_lane_max_pairs_per_wave();

@@ -26,12 +26,13 @@ __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, i
 // kernel that holds this call in a loop, whether or not an env is re-placed.
 // CAND: the small-list path first tries the candidate pass below (a.reset_thr, set at create).
 // N, thr: the agents placed and the candidate threshold -- a.N and a.reset_thr, or the env's own
-// (per-env parameters, kernels.h EnvParams).
+// (per-env parameters, kernels.h EnvParams).  F: the length of fl -- a.F, or the env's own room's
+// (per-env rooms: fl is then that room's list in the room table, keys still holds a.F pairs, the
+// largest room's count).
 template <int PWK = 0, bool SMALL = false, bool CAND = true>
 __device__ inline void wave_reset_env(const CoreStepArgs& a, uint32_t genv, unsigned long long* keys, const uint16_t* fl,
-                               uint16_t* gpos, int lane, int N, uint32_t thr) {
+                               uint16_t* gpos, int lane, int N, uint32_t thr, int F) {
     const int PW = PWK > 0 ? PWK : a.W + 2;
-    const int F = a.F;
     if (SMALL || F <= 128) {
         // lane holds keys j0 = lane and j1 = lane + 64 and ranks both in one pass over
         // 16-B broadcast reads of the key list (two keys per read; keys is 16-B aligned)
@@ -118,6 +119,13 @@ __device__ inline void wave_reset_env(const CoreStepArgs& a, uint32_t genv, unsi
         if (rank < N) gpos[rank] = (uint16_t)unpad(fl[(int)(ki & 0xFFFFu)], PW);
     }
     wave_sync();
+}
+
+// The engine's one room: a.F free cells.
+template <int PWK = 0, bool SMALL = false, bool CAND = true>
+__device__ inline void wave_reset_env(const CoreStepArgs& a, uint32_t genv, unsigned long long* keys, const uint16_t* fl,
+                               uint16_t* gpos, int lane, int N, uint32_t thr) {
+    wave_reset_env<PWK, SMALL, CAND>(a, genv, keys, fl, gpos, lane, N, thr, a.F);
 }
 
 // The engine-wide form: a.N agents, a.reset_thr.

@@ -14,17 +14,37 @@ import numpy as np
 FREE, AGENT, WALL, EXIT = 0, 1, 2, 3
 
 
-def make_room(H: int = 12, W: int = 12, exit_pos: tuple[int, int] | None = None) -> np.ndarray:
-    """Map per ``create_12x12_map_and_sff.py:15-25`` scaled to H x W (uint8)."""
+def make_room(H: int = 12, W: int = 12, exit_pos: tuple[int, int] | None = None,
+              exit_width: int = 1) -> np.ndarray:
+    """Map per ``create_12x12_map_and_sff.py:15-25`` scaled to H x W (uint8).
+
+    ``exit_width`` adjacent exit cells lie along the wall that holds ``exit_pos``: they start at
+    ``exit_pos`` and extend in +y on the top or bottom wall, in +x on a side wall.  A wider exit
+    that is not on a wall, or that would reach a corner, raises ValueError."""
     if H < 3 or W < 3:
         raise ValueError("room needs at least 3x3 cells")
+    if exit_width < 1:
+        raise ValueError("exit_width must be >= 1")
     m = np.zeros((H, W), dtype=np.uint8)
     m[0, :] = WALL
     m[-1, :] = WALL
     m[:, 0] = WALL
     m[:, -1] = WALL
     ex, ey = exit_pos if exit_pos is not None else (0, W // 2)
-    m[ex, ey] = EXIT
+    if exit_width == 1:
+        m[ex, ey] = EXIT
+        return m
+    ex, ey = ex % H, ey % W
+    if ex in (0, H - 1):      # top or bottom wall: along y
+        if ey < 1 or ey + exit_width > W - 1:
+            raise ValueError(f"a {exit_width}-wide exit at {(ex, ey)} would reach a corner of the {H}x{W} room")
+        m[ex, ey:ey + exit_width] = EXIT
+    elif ey in (0, W - 1):    # side wall: along x
+        if ex + exit_width > H - 1:
+            raise ValueError(f"a {exit_width}-wide exit at {(ex, ey)} would reach a corner of the {H}x{W} room")
+        m[ex:ex + exit_width, ey] = EXIT
+    else:
+        raise ValueError(f"a {exit_width}-wide exit must start on a wall, not at {(ex, ey)}")
     return m
 
 

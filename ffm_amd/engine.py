@@ -32,6 +32,7 @@ EXPORTED = [
     "ffm_engine_set_episode_log", "ffm_engine_drain_episodes", "ffm_engine_get_episode_stats",
     "ffm_debug_stage_image", "ffm_debug_reset_candidates",
     "ffm_engine_set_env_params", "ffm_engine_get_env_params", "ffm_engine_set_env_params_kernel",
+    "ffm_engine_set_env_rooms", "ffm_engine_get_env_rooms",
     "ffm_learner_create", "ffm_learner_destroy", "ffm_learner_reset", "ffm_learner_reset_envs", "ffm_learner_step",
     "ffm_learner_set_state", "ffm_learner_get_state", "ffm_learner_get_episodes",
     "ffm_learner_set_mt_state", "ffm_learner_get_mt_state", "ffm_learner_get_counters",
@@ -152,6 +153,8 @@ def load_library():
     L.ffm_engine_set_env_params.argtypes = [P, C.POINTER(EnvParams), i32, P, P]
     L.ffm_engine_get_env_params.argtypes = [P, C.POINTER(EnvParams), i32, C.POINTER(i32), P]
     L.ffm_engine_set_env_params_kernel.argtypes = [P, i32]
+    L.ffm_engine_set_env_rooms.argtypes = [P, P, P, i32, P, P]
+    L.ffm_engine_get_env_rooms.argtypes = [P, P, P, i32, C.POINTER(i32), P]
     L.ffm_np_expf_device.argtypes = [P, P, i64, P]
     L.ffm_debug_stage_image.argtypes = [P, P, i64, C.POINTER(i64)]
     L.ffm_debug_reset_candidates.argtypes = [P, C.POINTER(i32), C.POINTER(C.c_uint32)]
@@ -448,6 +451,53 @@ class Engine:
         _check(self._L.ffm_engine_get_env_params(self._h, arr, n.value, C.byref(n), _ptr(soe)))
         return [{k: getattr(q, k) for k in ENV_PARAM_KEYS} for q in arr], soe
 
+    # -- per-env rooms -----------------------------------------------------------
+    def set_env_rooms(self, rooms, room_of_env=None, stream=None):
+        """A geometry sweep in one engine (ffm_engine_set_env_rooms): env e runs in
+        rooms[room_of_env[e]] and evolves bit for bit like the env with the same global id of an
+        engine created with that room's map and SFF.  `rooms`: a sequence of (map, sff) array
+        pairs of the engine's shape (map codes as at create: 0 free, 2 wall, 3 exit; sff float32);
+        `room_of_env`: n_envs indices into it (default arange(n_envs) % len(rooms)).  Re-place
+        the envs whose room changed before stepping them: reset(), or reset_envs() over them.
+        rooms=None or []: off -- back to the create-time room, kernel and launch geometry.  While
+        on the engine steps with the lane kernel's room form, one launch per step
+        (launch_info()); it composes with set_env_params() in either order.  Lane and 12x12 group
+        engines only: MT, float64-SFF, wave and block engines raise NotImplementedError."""
+        rooms = list(rooms) if rooms is not None else []
+        if not rooms:
+            _check(self._L.ffm_engine_set_env_rooms(self._h, None, None, 0, None, _stream_handle(stream)))
+            return
+        maps = np.empty((len(rooms), self.H, self.W), np.uint8)
+        sffs = np.empty((len(rooms), self.H, self.W), np.float32)
+        for r, pair in enumerate(rooms):
+            m, f = pair
+            m, f = np.asarray(m), np.asarray(f)
+            if m.shape != (self.H, self.W) or f.shape != (self.H, self.W):
+                raise ValueError(f"room {r}: map and sff must have the engine's shape {(self.H, self.W)}, "
+                                 f"got {m.shape} and {f.shape}")
+            maps[r], sffs[r] = m, f
+        if room_of_env is None:
+            roe = (np.arange(self.n_envs) % len(rooms)).astype(np.int32)
+        else:
+            roe = np.ascontiguousarray(room_of_env, dtype=np.int32).reshape(-1)
+            if roe.size != self.n_envs:
+                raise ValueError(f"room_of_env must have n_envs = {self.n_envs} entries, got {roe.size}")
+        _check(self._L.ffm_engine_set_env_rooms(self._h, _ptr(maps), _ptr(sffs), len(rooms), _ptr(roe),
+                                                _stream_handle(stream)))
+
+    def env_rooms(self):
+        """(maps [R, H, W] uint8, sffs [R, H, W] float32, room_of_env [n_envs] int32) in effect
+        (ffm_engine_get_env_rooms), or None while the feature is off."""
+        n = C.c_int32()
+        _check(self._L.ffm_engine_get_env_rooms(self._h, None, None, 0, C.byref(n), None))
+        if n.value == 0:
+            return None
+        maps = np.empty((n.value, self.H, self.W), np.uint8)
+        sffs = np.empty((n.value, self.H, self.W), np.float32)
+        roe = np.empty(self.n_envs, np.int32)
+        _check(self._L.ffm_engine_get_env_rooms(self._h, _ptr(maps), _ptr(sffs), n.value, C.byref(n), _ptr(roe)))
+        return maps, sffs, roe
+
     # -- episode I/O ---------------------------------------------------------
     def set_trajectory_capture(self, envs, period: int = 1, phases=None, capacity_rows: int | None = None,
                                stream=None):
@@ -665,10 +715,14 @@ class Engine:
         workgroup K, the block size, the fused multi-step kernel's availability and grid, and the
         env shards a step(n > 1) call runs as under the current settings (1 = one launch per step
         over all envs) with the blocks of one shard's grid, and whether those launches take the
-        group kernel's single-group form ("group_one"; False: its loop form, or another kernel)."""
+        group kernel's single-group form ("group_one"; False: its loop form, or another kernel).
+        "env_rooms": the room count of set_env_rooms(), 0 while off (on: the lane kernel, one shard)."""
         v = np.zeros(10, np.int32)
         _check(self._L.ffm_debug_launch_info(self._h, _ptr(v), len(v)))
-        return {"kernel": ("group", "lane", "wave", "block", "block_scratch")[int(v[0])], "group_g": int(v[1]),
+        rooms = C.c_int32()
+        _check(self._L.ffm_engine_get_env_rooms(self._h, None, None, 0, C.byref(rooms), None))
+        return {"env_rooms": int(rooms.value),
+                "kernel": ("group", "lane", "wave", "block", "block_scratch")[int(v[0])], "group_g": int(v[1]),
                 "blocks": int(v[2]), "K": int(v[3]), "block_size": int(v[4]), "multi": bool(v[5]),
                 "multi_blocks": int(v[6]), "step_shards": int(v[7]), "shard_blocks": int(v[8]),
                 "group_one": bool(v[9])}

@@ -22,6 +22,14 @@ episodes.  ``steps_per_episode.csv`` then carries each env's own N and gains the
 
     python -m ffm_amd.evac --room 12 12 --sweep N=5,10,20,32 --sweep k_D=0,1,4 --envs 4096 --out runs/sweep
 
+Rooms sweep in the same engine too (``Engine.set_env_rooms``): ``--rooms MAP.npy:SFF.npy ...`` gives
+several rooms of one shape, and ``--sweep exit_width=1,2,4`` (with ``--room H W``) makes one room per
+width, the exit starting at the default position.  The room axis joins the Cartesian product as its
+slowest-varying axis (env e still runs combination e % P); both CSVs gain a ``room`` column (the room's
+index) and, when ``exit_width`` is swept, an ``exit_width`` column.  A room sweep needs no parameter sweep.
+
+    python -m ffm_amd.evac --room 12 12 --sweep exit_width=1,2,4 --sweep N=5,20,32 --envs 4096 --out runs/rooms
+
 ``--sweep-kernel {lane,group}`` picks the kernel that steps a sweep in a 12x12 engine (one born on
 the group kernel): the lane kernel's per-env form or the group kernel's own.  The outputs are
 the same bits either way; the default (SWEEP_KERNEL_DEFAULT) is the one that measured faster.
@@ -37,6 +45,7 @@ import numpy as np
 
 
 SWEEP_NAMES = ("k_S", "k_D", "diffuse", "decay", "N")
+ROOM_SWEEP_NAMES = ("exit_width",)   # swept through the room axis (--room H W), not a parameter set
 # The kernel of a sweep in an engine born on the group kernel when --sweep-kernel is not given
 # (every other engine has the one choice): the group kernel's own per-env form, which measured
 # faster than the lane kernel's in every run at 4,096, 32,768 and 65,536 envs (1.36, 1.64 and 1.66
@@ -45,30 +54,47 @@ SWEEP_KERNEL_DEFAULT = "group"
 
 
 def parse_sweep(text: str):
-    """``NAME=v1,v2,...`` -> (NAME, [values]); N values are ints, the others floats."""
+    """``NAME=v1,v2,...`` -> (NAME, [values]); N and exit_width values are ints, the others floats."""
     name, sep, vals = text.partition("=")
     name = name.strip()
-    if not sep or name not in SWEEP_NAMES:
-        raise ValueError(f"--sweep wants NAME=v1,v2,... with NAME one of {' '.join(SWEEP_NAMES)}: {text!r}")
+    if not sep or name not in SWEEP_NAMES + ROOM_SWEEP_NAMES:
+        raise ValueError("--sweep wants NAME=v1,v2,... with NAME one of "
+                         f"{' '.join(SWEEP_NAMES + ROOM_SWEEP_NAMES)}: {text!r}")
     items = [v for v in vals.split(",") if v.strip()]
     if not items:
         raise ValueError(f"--sweep {name}: no values")
-    return name, [int(v) if name == "N" else float(v) for v in items]
+    return name, [int(v) if name in ("N",) + ROOM_SWEEP_NAMES else float(v) for v in items]
 
 
-def sweep_grid(sweeps, base: dict) -> list:
+def sweep_grid(sweeps, base: dict, n_rooms: int = 0, exit_widths=None) -> list:
     """The parameter sets of a sweep: the Cartesian product of the (name, values) lists in
     argument order (the first name varies slowest), every other parameter from `base`.  Each
-    set is a dict with the keys k_S, k_D, diffuse, decay, N."""
+    set is a dict with the keys k_S, k_D, diffuse, decay, N.
+
+    With `n_rooms` > 0 the room is one more axis, the slowest of all: the combinations of room 0
+    come first, and every set also has "room" (the room's index) and, with `exit_widths` (one per
+    room), "exit_width"."""
     names = [n for n, _ in sweeps]
     if len(set(names)) != len(names):
         raise ValueError("--sweep: a name is given twice")
+    if exit_widths is not None and len(exit_widths) != n_rooms:
+        raise ValueError("one exit width per room")
     sets = []
-    for combo in itertools.product(*[v for _, v in sweeps]):
-        st = {k: base[k] for k in SWEEP_NAMES}
-        st.update(zip(names, combo))
-        sets.append(st)
+    for room in range(max(1, n_rooms)):
+        for combo in itertools.product(*[v for _, v in sweeps]):
+            st = {k: base[k] for k in SWEEP_NAMES}
+            st.update(zip(names, combo))
+            if n_rooms > 0:
+                st["room"] = room
+                if exit_widths is not None:
+                    st["exit_width"] = exit_widths[room]
+            sets.append(st)
     return sets
+
+
+def _room_cols(sets) -> tuple:
+    """The room columns the sets carry: (), ("room",) or ("room", "exit_width")."""
+    return tuple(c for c in ("room",) + ROOM_SWEEP_NAMES if sets and c in sets[0])
 
 
 def env_assignment(n_envs: int, n_sets: int) -> np.ndarray:
@@ -94,11 +120,11 @@ def steps_csv(records: np.ndarray, episodes: int, N: int, sets=None, set_of_env=
         for env, k, steps, _ in rec.tolist():
             lines.append(f"{env * episodes + k + 1},{env},{N},{steps}")
         return "\n".join(lines) + "\n"
-    lines = ["episode_num,env,N,steps,k_S,k_D,diffuse,decay"]
+    cols = ("k_S", "k_D", "diffuse", "decay") + _room_cols(sets)   # a room sweep: room[, exit_width] follow
+    lines = ["episode_num,env,N,steps," + ",".join(cols)]
     for env, k, steps, _ in rec.tolist():
         st = sets[int(set_of_env[env - env_base])]
-        lines.append(f"{env * episodes + k + 1},{env},{st['N']},{steps}," +
-                     ",".join(_num(st[c]) for c in ("k_S", "k_D", "diffuse", "decay")))
+        lines.append(f"{env * episodes + k + 1},{env},{st['N']},{steps}," + ",".join(_num(st[c]) for c in cols))
     return "\n".join(lines) + "\n"
 
 
@@ -107,10 +133,11 @@ def sweep_summary_csv(steps: np.ndarray, sets, set_of_env) -> str:
     std, min, max of the evacuation times [E, per_env] of its envs."""
     steps = np.asarray(steps)
     soe = np.asarray(set_of_env)
-    lines = ["set,k_S,k_D,diffuse,decay,N,count,mean,std,min,max"]
+    cols = ("k_S", "k_D", "diffuse", "decay", "N") + _room_cols(sets)   # a room sweep: room[, exit_width] follow N
+    lines = ["set," + ",".join(cols) + ",count,mean,std,min,max"]
     for p, st in enumerate(sets):
         s = steps[soe == p].astype(np.float64).reshape(-1)
-        head = f"{p}," + ",".join(_num(st[c]) for c in ("k_S", "k_D", "diffuse", "decay", "N"))
+        head = f"{p}," + ",".join(_num(st[c]) for c in cols)
         if s.size == 0:
             lines.append(head + ",0,nan,nan,0,0")
         else:
@@ -139,6 +166,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--map", help=".npy map (0 free, 2 wall, 3 exit)")
     ap.add_argument("--sff", help=".npy static floor field of the map")
     ap.add_argument("--room", nargs=2, type=int, metavar=("H", "W"), help="a walled H x W room with one exit")
+    ap.add_argument("--rooms", nargs="+", metavar="MAP.npy:SFF.npy",
+                    help="several rooms of one shape in one engine (the room axis of the sweep)")
     ap.add_argument("--N", type=int, default=32, help="agents per env")
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--episodes", type=int, default=1, help="evacuations per env")
@@ -150,7 +179,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--neighborhood", choices=("neumann", "moore"), default="moore")
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--sweep", action="append", default=[], metavar="NAME=v1,v2,...",
-                    help="sweep k_S, k_D, diffuse, decay or N in one engine (repeatable: Cartesian product)")
+                    help="sweep k_S, k_D, diffuse, decay, N or (with --room) exit_width in one engine "
+                         "(repeatable: Cartesian product)")
     ap.add_argument("--sweep-kernel", choices=("lane", "group"), default=None,
                     help="the kernel that steps a sweep in an engine born on the group kernel (12x12): the lane "
                          f"kernel's per-env form or the group kernel's own (default: {SWEEP_KERNEL_DEFAULT}; "
@@ -162,38 +192,63 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
-    if bool(a.map) != bool(a.sff) or bool(a.map) == bool(a.room):
-        ap.error("give either --map and --sff, or --room H W")
+    if bool(a.map) != bool(a.sff) or sum(map(bool, (a.map, a.room, a.rooms))) != 1:
+        ap.error("give either --map and --sff, or --room H W, or --rooms MAP.npy:SFF.npy ...")
 
     from .data import l1_sff, make_room
     from .engine import Engine
-    if a.room:
-        m = make_room(*a.room)
-        sff = l1_sff(m)
-    else:
-        m, sff = np.load(a.map), np.load(a.sff)
     params = {"k_S": a.k_S, "k_D": a.k_D, "diffuse": a.diffuse, "decay": a.decay, "neighborhood": a.neighborhood}
+    rooms = widths = None      # the room axis: (map, sff) pairs, and the exit widths that made them
     sets = soe = None
     n_max = a.N
-    if a.sweep:
-        try:
-            sets = sweep_grid([parse_sweep(t) for t in a.sweep], {**params, "N": a.N})
+    try:
+        sweeps = [parse_sweep(t) for t in a.sweep]
+        room_sweeps = [sw for sw in sweeps if sw[0] in ROOM_SWEEP_NAMES]
+        sweeps = [sw for sw in sweeps if sw[0] not in ROOM_SWEEP_NAMES]
+        if len(room_sweeps) > 1:
+            raise ValueError("--sweep: a name is given twice")
+        if room_sweeps and not a.room:
+            raise ValueError("--sweep exit_width wants --room H W")
+        if room_sweeps:
+            widths = room_sweeps[0][1]
+            maps = [make_room(*a.room, exit_pos=(0, a.room[1] // 2), exit_width=w) for w in widths]
+            rooms = [(mp, l1_sff(mp)) for mp in maps]
+        elif a.rooms:
+            rooms = []
+            for text in a.rooms:
+                mp, sep, sf = text.partition(":")
+                if not sep:
+                    raise ValueError(f"--rooms wants MAP.npy:SFF.npy, got {text!r}")
+                rooms.append((np.load(mp), np.load(sf).astype(np.float32)))
+        if rooms:
+            m, sff = rooms[0]
+        elif a.room:
+            m = make_room(*a.room)
+            sff = l1_sff(m)
+        else:
+            m, sff = np.load(a.map), np.load(a.sff)
+        if sweeps or rooms:
+            sets = sweep_grid(sweeps, {**params, "N": a.N}, len(rooms) if rooms else 0, widths)
             soe = env_assignment(a.envs, len(sets))
-        except ValueError as err:
-            ap.error(str(err))
-        n_max = max(st["N"] for st in sets)   # the agent capacity
+            n_max = max(st["N"] for st in sets)   # the agent capacity
+    except ValueError as err:
+        ap.error(str(err))
     eng = Engine(m, sff, n_envs=a.envs, n_agents=n_max, params=params, rng="philox", seed=a.seed,
                  auto_reset=a.episodes > 1)
-    if sets:   # before the reset: its placement takes each env's own N
-        kernel = a.sweep_kernel
-        if kernel is None and eng.launch_info()["kernel"] == "group":
-            kernel = SWEEP_KERNEL_DEFAULT
-        try:
+    try:   # before the reset: its placement takes each env's own room and N
+        if rooms:
+            eng.set_env_rooms(rooms, np.array([sets[p]["room"] for p in soe], np.int32))
+        if sets and (sweeps or not rooms):
+            # the room axis is the slowest: combination c has the parameters of combination c % Pp
+            n_par = len(sets) // max(1, len(rooms) if rooms else 1)
+            kernel = a.sweep_kernel
+            if kernel is None and eng.launch_info()["kernel"] == "group":
+                kernel = SWEEP_KERNEL_DEFAULT
             eng.set_env_params([{"k_S": st["k_S"], "k_D": st["k_D"], "diffuse": st["diffuse"], "decay": st["decay"],
-                                 "n_agents": st["N"]} for st in sets], soe, kernel=kernel)
-        except NotImplementedError as err:   # --sweep-kernel group on an engine of another kernel
-            eng.close()
-            ap.error(str(err))
+                                 "n_agents": st["N"]} for st in sets[:n_par]], soe % n_par, kernel=kernel)
+    except (NotImplementedError, ValueError) as err:   # e.g. --sweep-kernel group on an engine of another kernel
+        eng.close()
+        ap.error(str(err))
     eng.set_episode_log(hist_bins=0)
     eng.reset()
     t0 = time.perf_counter()

@@ -283,6 +283,60 @@ int ffm_engine_get_env_params(ffm_engine* eng, ffm_env_params* sets, int32_t cap
  * nothing changes.  Other modes: FFM_E_INVALID. */
 int ffm_engine_set_env_params_kernel(ffm_engine* eng, int32_t mode);
 
+/* Per-env rooms: a geometry sweep (exit width, exit position, obstacles) in one engine, where
+ * the reference edits Create_Map.py / Create_SFF.py and re-runs main.py per room.
+ *
+ * While the feature is on, env e (global id env_base + e) runs in room rooms[room_of_env[e]] and
+ * evolves bit for bit like the env with the same global id of a homogeneous engine created with
+ * that room's map and SFF and the same neighbourhood, seed, auto_reset and step indices (and,
+ * with per-env parameters on as well, that env's parameter set): positions, counts, DFF bits,
+ * episodes, counters, episode-log records and trajectory rows.  (Every Philox draw is keyed by
+ * (seed, t, global env, agent, purpose); the placement ranks keys indexed by the position in the
+ * env's own room's free list, with that room's free-cell count.)
+ *
+ * maps: host [n_rooms][H*W] uint8 (0 free, 2 wall, 3 exit, as ffm_engine_desc.map);
+ * sffs: host [n_rooms][H*W] float32; room_of_env: host [n_envs] indices into the rooms.
+ * n_rooms = 0 turns the feature off (create-time room, kernel and launch geometry again).
+ *
+ * Validated before anything changes; a failed call leaves the engine exactly as it was.
+ * FFM_E_INVALID: n_rooms outside 1 <= n_rooms <= n_envs; a free cell on a room's border; a
+ * room_of_env entry out of range; null tables; an env whose n_agents -- the create-time one, or
+ * its parameter set's while per-env parameters are on -- exceeds the free cells of its own room
+ * (ffm_engine_set_env_params makes the same per-env check while rooms are on; turning rooms off
+ * checks every set against the create-time room).  FFM_E_UNSUPPORTED: MT engines, float64-SFF
+ * engines, and engines on which the lane kernel cannot run (agent_capacity > 32, W % 4 != 0,
+ * H*W > 256, or its LDS at the largest room's free-cell count beyond 64 KB).
+ *
+ * Scope: 12x12 group engines and lane engines.  Wave and block engines have no room form yet.
+ *
+ * May be called between steps; stream-ordered on `stream`, which it synchronises: the tables are
+ * consumed before it returns.  The room holds from the next launch.  An env whose room changes
+ * must be re-placed before it is stepped again (ffm_engine_reset, or ffm_engine_reset_envs over
+ * those envs; the normal order is create, set_env_rooms, reset).  Stepping agents that were
+ * placed in another room gives undefined results for that env but stays memory-safe: every access
+ * a step makes stays inside the env's own padded grid, tile and position row, no index is derived
+ * from a map code, and the envs stepped after it by the same wave see their own room unchanged.
+ *
+ * With per-env parameters: the two compose in either call order, with the same bits.  While rooms
+ * are on the kernel has a parameter record per env; without ffm_engine_set_env_params the records
+ * hold the create-time values.  Each env's placement-candidate threshold is computed with its
+ * room's free-cell count by the expression create uses (FFM_RESET_CANDIDATES is honoured).
+ * Turning either feature off rebuilds what the other needs.
+ *
+ * Kernel: while rooms are on the engine steps with the lane kernel's room form, one launch per
+ * step: step shards and fused steps are off (ffm_engine_set_fused_steps(k > 1) is accepted and
+ * ignored meanwhile, as under trajectory capture), and a sticky
+ * ffm_engine_set_env_params_kernel(eng, 1) is remembered and resumes when rooms are turned off.
+ * Trajectory capture, the episode log and statistics, ffm_engine_reset_envs,
+ * ffm_engine_update_dff (map-independent), ffm_engine_get_state / ffm_engine_set_state (which
+ * checks positions against the env's own room) and a stream under capture work unchanged. */
+int ffm_engine_set_env_rooms(ffm_engine* eng, const uint8_t* maps, const float* sffs, int32_t n_rooms,
+                             const int32_t* room_of_env, void* stream);
+/* *n_rooms = 0 while off; maps / sffs (cap rooms) and room_of_env may be NULL;
+ * cap < *n_rooms: FFM_E_INVALID with *n_rooms = the count needed. */
+int ffm_engine_get_env_rooms(ffm_engine* eng, uint8_t* maps, float* sffs, int32_t cap, int32_t* n_rooms,
+                             int32_t* room_of_env);
+
 /* counters[4] = {agent_steps, exits, resets, steps} accumulated since create. */
 int ffm_engine_get_counters(ffm_engine* eng, uint64_t* counters, void* stream);
 int ffm_engine_device_buffers(ffm_engine* eng, ffm_device_buffers* out);
