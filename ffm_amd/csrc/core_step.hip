@@ -651,20 +651,35 @@ __device__ __forceinline__ int block_excl_scan(bool flag, int* swsum, int& total
 // with the smallest (key_j, j).  Candidates under a threshold (~2N + 16 of them) are
 // kept in `keys` (KC of them) and ranked; more than KC take an exact recomputing path.
 // PEP: the env's own N (per-env parameters, a.envp).
-template <int BS, bool PEP = false>
+// ROOM (with PEP): F and the free list of the env's own room, from its record of the room table
+// (kernels.h room_layout; padded indices, turned into the row-major cells a.pos takes); a.F is the
+// largest room's, which sizes KC and the carve.
+template <int BS, bool PEP = false, bool ROOM = false>
 __device__ void block_place_env(const CoreStepArgs& a, long long e, unsigned long long* keys, int KC, int* swsum) {
+    static_assert(PEP || !ROOM, "the room form takes every env's record");
     const int tid = threadIdx.x;
     const uint32_t genv = (uint32_t)(a.env_base + e);
     const int N = PEP ? a.envp[e].N : a.N;
-    uint32_t T = reset_threshold(N, a.F);
+    int F = a.F;
+    const uint16_t* fl = a.free_list;
+    if constexpr (ROOM) {
+        const unsigned char* rec = a.rooms + (size_t)a.room_of_env[e] * (size_t)a.room_stride;
+        F = min(*reinterpret_cast<const int*>(rec), a.F);   // the record's list holds a.F entries
+        fl = reinterpret_cast<const uint16_t*>(rec + room_layout((a.H + 2) * (a.W + 2), a.F).free);
+    }
+    // the cell a.pos takes of free-list entry j
+    auto cell_of = [&](int j) -> uint16_t {
+        return ROOM ? (uint16_t)unpad_m(fl[j], a.W + 2, a.mPW) : fl[j];
+    };
+    uint32_t T = reset_threshold(N, F);
     int C = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
         C = 0;
-        for (int j0 = 0; j0 < a.F; j0 += BS) {
+        for (int j0 = 0; j0 < F; j0 += BS) {
             const int j = j0 + tid;
             uint32_t key = 0;
             bool cand = false;
-            if (j < a.F) {
+            if (j < F) {
                 key = reset_key(a.key0, a.key1, a.t, genv, (uint32_t)j);
                 cand = key <= T;
             }
@@ -684,21 +699,21 @@ __device__ void block_place_env(const CoreStepArgs& a, long long e, unsigned lon
             int rank = 0;
 #pragma unroll 4
             for (int q = 0; q < C; q++) rank += keys[q] < ki ? 1 : 0;
-            if (rank < N) a.pos[e * a.A + rank] = a.free_list[(int)(ki & 0xFFFFFFFFu)];
+            if (rank < N) a.pos[e * a.A + rank] = cell_of((int)(ki & 0xFFFFFFFFu));
         }
     } else {
         // Exact but slow (keys recomputed per comparison): the candidates exceed KC.
-        for (int j = tid; j < a.F; j += BS) {
+        for (int j = tid; j < F; j += BS) {
             const uint32_t kj = reset_key(a.key0, a.key1, a.t, genv, (uint32_t)j);
             if (kj > T) continue;
             const unsigned long long ki = ((unsigned long long)kj << 32) | (unsigned)j;
             int rank = 0;
-            for (int q = 0; q < a.F && rank < N; q++) {
+            for (int q = 0; q < F && rank < N; q++) {
                 const unsigned long long kq =
                     ((unsigned long long)reset_key(a.key0, a.key1, a.t, genv, (uint32_t)q) << 32) | (unsigned)q;
                 rank += kq < ki ? 1 : 0;
             }
-            if (rank < N) a.pos[e * a.A + rank] = a.free_list[j];
+            if (rank < N) a.pos[e * a.A + rank] = cell_of(j);
         }
     }
     __syncthreads();
@@ -726,10 +741,15 @@ __device__ __forceinline__ CT req_cell(uint32_t slot, int pp, int PW) {
 // EPL: as core_wave_kernel's.  PEP (Philox only): per-env parameters -- the block's K records
 // (a.envp, kernels.h) are staged into LDS behind the carve in the prologue; decide takes the
 // agent's env's kS32 / kD32 / kS64, the stencil the cell's env's c0 / c1, the count store and the
-// placement the env's N.
-template <int NB, bool F64, bool MT, int BS, bool BIG, bool EPL, bool PEP>
+// placement the env's N.  ROOM (with PEP; float32 SFF, LDS-sized maps): per-env rooms -- the K
+// envs' room indices are staged behind the records; an env's grid starts as its room's u16 codes,
+// decide reads its room's SFF, the exit test its room's codes and the placement its room's F and
+// free list, all from the room table in global memory (a.rooms, kernels.h room_layout).
+template <int NB, bool F64, bool MT, int BS, bool BIG, bool EPL, bool PEP, bool ROOM = false>
 __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(NB == 4 && !F64 ? FFM_BLOCK_WAVES : 1, 8)))
 void core_block_kernel(CoreStepArgs a) {
+    static_assert(PEP || !ROOM, "the room form takes every env's record");
+    static_assert(!ROOM || (!F64 && !MT && !BIG), "the room form: Philox, float32 SFF, state in LDS");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     using GT = uint16_t;
     using CT = typename std::conditional<BIG, uint32_t, uint16_t>::type;
@@ -758,6 +778,10 @@ void core_block_kernel(CoreStepArgs a) {
     int* swsum = sseg + a.K;                               // [BS/64]
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(gbase + cv.keys);
     const EnvParams* const sp = reinterpret_cast<const EnvParams*>(smem + cv.lds);   // PEP: [K], past the carve
+    int* const sroom = reinterpret_cast<int*>(smem + cv.lds + (size_t)a.K * sizeof(EnvParams));   // ROOM: [K] room indices
+    const RoomLayout lay = room_layout(PHW, a.F);   // ROOM: the parts of a room's record
+    // ROOM: the record of env k's room (after the prologue's barrier)
+    auto room_rec = [&](int k) { return a.rooms + (size_t)sroom[k] * (size_t)a.room_stride; };
 
     const int nA = K * A;
     const int nP = K * PHW;
@@ -786,6 +810,25 @@ void core_block_kernel(CoreStepArgs a) {
             }
         // every env's grid starts as the map: four u8 cells per load, two u16 dwords per store
         // (W % 4 == 0: PW and PHW are even, so each env's grid is dword aligned)
+        if constexpr (ROOM) {
+            // every env's grid starts as its room's u16 codes: 16-byte loads from the record (its
+            // grid part is 16-byte aligned and a whole number of 16-byte words), dword stores (an
+            // env's LDS grid is only dword aligned: k * PHW * 2 bytes, PHW even).  The room index
+            // comes straight from global memory: sroom is not staged yet.
+            const int P2 = PHW >> 1, Q = (P2 + 3) >> 2;
+            for (int k = 0; k < K; k++) {
+                const uint4* src = reinterpret_cast<const uint4*>(
+                    a.rooms + (size_t)a.room_of_env[e0 + k] * (size_t)a.room_stride + lay.grid);
+                uint32_t* g32 = reinterpret_cast<uint32_t*>(grid + k * PHW);
+                for (int i = tid; i < Q; i += BS) {
+                    const uint4 v = src[i];
+                    if (4 * i < P2) g32[4 * i] = v.x;
+                    if (4 * i + 1 < P2) g32[4 * i + 1] = v.y;
+                    if (4 * i + 2 < P2) g32[4 * i + 2] = v.z;
+                    if (4 * i + 3 < P2) g32[4 * i + 3] = v.w;
+                }
+            }
+        } else {
         const uint32_t* m32 = reinterpret_cast<const uint32_t*>(a.pmap);
         const int P4 = PHW >> 2;
         for (int k = 0; k < K; k++) {
@@ -797,12 +840,17 @@ void core_block_kernel(CoreStepArgs a) {
             }
             for (int i = 4 * P4 + tid; i < PHW; i += BS) grid[k * PHW + i] = a.pmap[i];
         }
+        }
     } else {
         Idx3 ix(tid, BS, H + 2, PW);
         for (int i = tid; i < nP; i += BS, ix.advance()) {
             const int x = ix.r - 1, y = ix.c - 1, pc = ix.r * PW + ix.c;
             const bool in = x >= 0 && x < H && y >= 0 && y < W;
             tile[i] = in ? a.dff[(e0 + ix.k) * HW + x * W + y] : 0.0f;
+            if constexpr (ROOM)   // the env's room's code (u16 loads: the LDS grid may be only 2-byte aligned)
+                grid[i] = reinterpret_cast<const uint16_t*>(
+                    a.rooms + (size_t)a.room_of_env[e0 + ix.k] * (size_t)a.room_stride + lay.grid)[pc];
+            else
             grid[i] = a.pmap[pc];
         }
     }
@@ -814,6 +862,9 @@ void core_block_kernel(CoreStepArgs a) {
         const uint32_t* src = reinterpret_cast<const uint32_t*>(a.envp + e0);
         uint32_t* dst = reinterpret_cast<uint32_t*>(smem + cv.lds);
         for (int i = tid; i < K * (int)(sizeof(EnvParams) / 4); i += BS) dst[i] = src[i];
+    }
+    if constexpr (ROOM) {   // the K envs' room indices (the last block may hold fewer than a.K envs)
+        if (tid < K) sroom[tid] = a.room_of_env[e0 + tid];
     }
     __syncthreads();
     for (AgentIdx ag = ag0; ag.it < nA; ag.advance()) {
@@ -858,6 +909,10 @@ void core_block_kernel(CoreStepArgs a) {
                                           a.key0, a.key1);
             reinterpret_cast<uint2*>(gbase + cv.u)[it] = make_uint2(pb.z, pb.w);
             const float kS32 = PEP ? sp[k].kS32 : a.kS32, kD32 = PEP ? sp[k].kD32 : a.kD32;
+            // ROOM: the env's room's padded SFF (halo 0, interior cells the caller's values, as a.psff)
+            // (FFM_BLOCK_ABLATE & 16, the mutation check of DESIGN.md 3.7: the block's first env's SFF for all K)
+            const float* const sff = ROOM ? reinterpret_cast<const float*>(room_rec((FFM_BLOCK_ABLATE & 16) ? 0 : k) + lay.sff)
+                                          : psff32;
             if (F64) {
                 r = req_cell<NB, CT>(decide<NB, F64, GT>(pp, PW, grid + k * PHW, psff32, psff64, tile + k * PHW, 0, 0,
                                                          kS32, kD32, PEP ? sp[k].kS64 : a.kS64,
@@ -868,12 +923,12 @@ void core_block_kernel(CoreStepArgs a) {
                 // pass only when u lies within the margin of a cdf boundary (identical results)
                 bool to_exit = false;
                 uint32_t slot = (FFM_BLOCK_ABLATE & 8) ? (uint32_t)NB   // diagnostic: everyone stays
-                                : lane_decide<NB, false, false, 0>(pp, PW, grid + k * PHW, psff32, tile + k * PHW, 0,
+                                : lane_decide<NB, false, false, 0>(pp, PW, grid + k * PHW, sff, tile + k * PHW, 0,
                                                                  kS32, kD32, pb.x, to_exit);
                 if (slot == kPending)
-                    slot = NB == 4 ? lane_decide_exact<NB, false, 0>(pp, PW, grid + k * PHW, psff32, tile + k * PHW, 0,
+                    slot = NB == 4 ? lane_decide_exact<NB, false, 0>(pp, PW, grid + k * PHW, sff, tile + k * PHW, 0,
                                                                      kS32, kD32, u53(pb.x, pb.y))
-                                   : lane_decide_exact_arr<NB, false, 0>(pp, PW, grid + k * PHW, psff32, tile + k * PHW,
+                                   : lane_decide_exact_arr<NB, false, 0>(pp, PW, grid + k * PHW, sff, tile + k * PHW,
                                                                          0, kS32, kD32, u53(pb.x, pb.y));
                 r = req_cell<NB, CT>(slot, pp, PW);
             }
@@ -990,7 +1045,11 @@ void core_block_kernel(CoreStepArgs a) {
             const int it = base + tid;
             const int k = ex.k, i = ex.i;
             const bool live = it < nA && i < scnt[k];
-            const bool keep = live && pmap[snxt[it]] != 3;
+            bool keep;
+            if constexpr (ROOM)   // the env's room's code of the cell
+                keep = live && reinterpret_cast<const uint16_t*>(room_rec(k) + lay.grid)[snxt[it]] != 3;
+            else
+                keep = live && pmap[snxt[it]] != 3;
             int tot;
             const int excl = carry + block_excl_scan<BS>(keep, swsum, tot);
             if (it < nA && i == 0) sseg[k] = excl;
@@ -1011,7 +1070,7 @@ void core_block_kernel(CoreStepArgs a) {
         __syncthreads();
         for (int k = 0; k < K; k++) {
             if (!sreset[k]) continue;   // block-uniform
-            block_place_env<BS, PEP>(a, e0 + k, keys, KC, swsum);
+            block_place_env<BS, PEP, ROOM>(a, e0 + k, keys, KC, swsum);
         }
     }
 
@@ -1132,8 +1191,10 @@ __global__ __launch_bounds__(64) void core_reset_kernel(CoreStepArgs a, const ui
 
 // Reset every env of a map whose free list does not fit the wave reset's LDS
 // (big maps): one workgroup per env, keys in the env block's global scratch.
-template <bool PEP>
+// ROOM (with PEP): as core_reset_kernel's -- the env's own room's F and free list (block_place_env).
+template <bool PEP, bool ROOM = false>
 __global__ __launch_bounds__(1024) void core_block_reset_kernel(CoreStepArgs a, const uint8_t* mask) {
+    static_assert(PEP || !ROOM, "the room form takes every env's record");
     __shared__ int swsum[16];
     const long long e = blockIdx.x;
     if (mask) {   // as core_reset_kernel
@@ -1144,7 +1205,7 @@ __global__ __launch_bounds__(1024) void core_block_reset_kernel(CoreStepArgs a, 
     }
     const BlockCarve cv = block_carve((a.H + 2) * (a.W + 2), a.A, 1, a.F, false, false, true, true);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(a.scratch + (size_t)e * a.scratch_stride + cv.keys);
-    block_place_env<1024, PEP>(a, e, keys, block_keys_cap(a.A, a.F), swsum);
+    block_place_env<1024, PEP, ROOM>(a, e, keys, block_keys_cap(a.A, a.F), swsum);
     if (threadIdx.x == 0) {
         a.cnt[e] = PEP ? a.envp[e].N : a.N;
         eplog_mark_start(a, e, a.t);
@@ -1257,11 +1318,24 @@ int core_wave_blocks_per_cu(const CoreStepArgs& a, int nb, bool mt) {
 }
 
 size_t core_block_pep_smem_bytes(int K) { return (size_t)K * sizeof(EnvParams); }
+size_t core_block_room_smem_bytes(int K) { return (size_t)K * (sizeof(EnvParams) + 4); }
 
 template <int NB, bool F64, bool MT, int BS, bool BIG>
 static hipError_t launch_block_bs(const CoreStepArgs& a, long long nblk, size_t smem, hipStream_t s) {
     const dim3 gd((unsigned)nblk), bd(BS);
     const bool epl = !MT && a.ep_start;
+    if (a.rooms) {   // per-env rooms: the K records and room indices behind the carve
+        if constexpr (!F64 && !MT && !BIG) {
+            const size_t sr = smem + core_block_room_smem_bytes(a.K);
+            if (!a.envp || !a.room_of_env || sr > 64 * 1024)
+                return hipErrorInvalidConfiguration;   // host-checked (ffm_engine_set_env_rooms)
+            if (epl) core_block_kernel<NB, F64, MT, BS, BIG, true, true, true><<<gd, bd, sr, s>>>(a);
+            else core_block_kernel<NB, F64, MT, BS, BIG, false, true, true><<<gd, bd, sr, s>>>(a);
+            return hipGetLastError();
+        } else {
+            return hipErrorInvalidConfiguration;   // the room form: Philox, float32 SFF, state in LDS
+        }
+    }
     if (!MT && a.envp) {   // per-env parameters: the K records behind the carve
         const size_t sp = smem + core_block_pep_smem_bytes(a.K);
         if (sp > 64 * 1024) return hipErrorInvalidConfiguration;   // host-checked (ffm_engine_set_env_params)
@@ -1293,7 +1367,8 @@ hipError_t launch_core_block(const CoreStepArgs& a, int nb, bool f64, bool mt, i
 }
 
 hipError_t launch_core_block_reset(const CoreStepArgs& a, hipStream_t s, const uint8_t* mask) {
-    if (a.envp) core_block_reset_kernel<true><<<dim3((unsigned)a.E), dim3(1024), 0, s>>>(a, mask);
+    if (a.rooms) core_block_reset_kernel<true, true><<<dim3((unsigned)a.E), dim3(1024), 0, s>>>(a, mask);
+    else if (a.envp) core_block_reset_kernel<true><<<dim3((unsigned)a.E), dim3(1024), 0, s>>>(a, mask);
     else core_block_reset_kernel<false><<<dim3((unsigned)a.E), dim3(1024), 0, s>>>(a, mask);
     return hipGetLastError();
 }

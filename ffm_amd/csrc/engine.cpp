@@ -121,14 +121,17 @@ struct ffm_engine {
     unsigned char* d_stage_raw = nullptr;      // its stage image: the SFF term with multiplier 1 (the raw SFF);
                                                // built when the feature first moves to the group kernel
     // Per-env rooms (ffm_engine_set_env_rooms): null / empty while off.  While on the engine steps
-    // with the lane kernel's room form and d_envp holds a record per env: the caller's sets', or
-    // (pep_sets empty) the create-time values, each with its room's placement threshold.
+    // with the lane kernel's room form, or (room_block) the block kernel's, and d_envp holds a
+    // record per env: the caller's sets', or (pep_sets empty) the create-time values, each with
+    // its room's placement threshold.
     bool lane_ok = false;                      // the lane kernel's conditions hold (create)
     unsigned char* d_rooms = nullptr;          // the room table (kernels.h room_layout)
     int32_t* d_room_of_env = nullptr;          // [n_envs]
     size_t room_stride = 0;
     int room_fmax = 0;                         // the largest room's free-cell count
-    int room_lane_blocks = 0;                  // the room form's persistent grid
+    int room_lane_blocks = 0;                  // the lane room form's persistent grid
+    int room_kernel = 0;                       // ffm_engine_set_env_rooms_kernel's mode (sticky)
+    bool room_block = false;                   // rooms are on in the block kernel's form (mode 1)
     std::vector<uint8_t> room_maps;            // the caller's tables, for ffm_engine_get_env_rooms
     std::vector<float> room_sffs;
     std::vector<int32_t> room_of_env;
@@ -144,7 +147,8 @@ static bool pep_on(const ffm_engine* e) { return e->d_envp && !e->pep_sets.empty
 static bool pep_group_on(const ffm_engine* e) { return !rooms_on(e) && e->d_envp && e->pep_group; }
 static bool steps_group(const ffm_engine* e) { return !rooms_on(e) && e->group && (!e->d_envp || e->pep_group); }
 static bool steps_lane(const ffm_engine* e) {
-    return rooms_on(e) || (e->d_envp ? e->pep_lane && !e->pep_group : e->lane);
+    if (rooms_on(e)) return !e->room_block;
+    return e->d_envp ? e->pep_lane && !e->pep_group : e->lane;
 }
 static bool steps_wave(const ffm_engine* e) { return e->wave && !e->d_envp; }
 // Blocks per CU of the group kernel's largest grid (engine create, group_grid).
@@ -1288,6 +1292,7 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
         e->room_stride = 0;
         e->room_fmax = 0;
         e->room_lane_blocks = 0;
+        e->room_block = false;
         e->room_maps.clear();
         e->room_sffs.clear();
         e->room_of_env.clear();
@@ -1296,7 +1301,10 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     }
     if (e->mt) return fail(FFM_E_UNSUPPORTED, "env rooms: Philox engines only");
     if (e->f64) return fail(FFM_E_UNSUPPORTED, "env rooms: float32-SFF engines only");
-    if (!e->lane_ok)
+    // the block kernel's room form where the engine's setting asks for it (ffm_engine_set_env_rooms_kernel,
+    // which accepted the engine); else the lane kernel's
+    const bool block_form = e->room_kernel == 1;
+    if (!block_form && !e->lane_ok)
         return fail(FFM_E_UNSUPPORTED, "env rooms: engines of the lane kernel's shapes only (agent_capacity <= 32, W % 4 == 0, H*W <= 256)");
     if (n_rooms < 1 || n_rooms > e->d.n_envs) return fail(FFM_E_INVALID, "env rooms: n_rooms must lie in [0, n_envs]");
     if (!maps || !sffs || !room_of_env) return fail(FFM_E_INVALID, "env rooms: maps, sffs and room_of_env are required");
@@ -1319,8 +1327,23 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     }
     for (size_t i = 0; i < E; i++)
         if (room_of_env[i] < 0 || room_of_env[i] >= n_rooms) return fail(FFM_E_INVALID, "env rooms: room_of_env out of range");
-    if (ffm::core_lane_smem_bytes(H, W, fmax, 4, true) > 64 * 1024)
+    if (!block_form && ffm::core_lane_smem_bytes(H, W, fmax, 4, true) > 64 * 1024)
         return fail(FFM_E_UNSUPPORTED, "env rooms: the lane kernel's LDS has no room for the largest room");
+    if (block_form) {
+        // the block kernel at the create-time K with the largest room's F, the K records and room indices
+        if (ffm::core_block_smem_bytes(H, W, e->d.agent_capacity, e->K, fmax, false, false, e->d.auto_reset != 0) +
+                ffm::core_block_room_smem_bytes(e->K) > 64 * 1024)
+            return fail(FFM_E_UNSUPPORTED, "env rooms: the block kernel's LDS has no room for the largest room and the K records");
+        // the placement of the largest room: in the block reset's scratch (sized at create), or in
+        // the wave reset's LDS (launch_core_reset's carve)
+        auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+        if (e->block_reset ? ffm::core_big_scratch_bytes(H, W, e->d.agent_capacity, fmax, false) > e->scratch_stride
+                           : al16(8 * (size_t)std::max(1, fmax)) + al16(2 * (size_t)e->d.agent_capacity) +
+                                     al16(2 * (size_t)std::max(1, fmax)) > 64 * 1024)
+            return fail(FFM_E_UNSUPPORTED, "env rooms: the placement has no room for the largest room's free list");
+        if ((size_t)((e->d.n_envs + e->K - 1) / e->K) > e->ctr_slots)
+            return fail(FFM_E_UNSUPPORTED, "env rooms: counter slots");
+    }
     const ffm_env_params* sets = pep ? e->pep_sets.data() : nullptr;
     const int32_t* set_of_env = pep ? e->pep_set_of_env.data() : nullptr;
     if (env_over_capacity(e, sets, set_of_env, &room_f, room_of_env) >= 0)
@@ -1368,7 +1391,7 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     if (he == hipSuccess) he = hipMalloc((void**)&d_envp, E * sizeof(ffm::EnvParams));
     if (he != hipSuccess) return undo(fail(FFM_E_NOMEM, std::string("env rooms: ") + hipGetErrorString(he)));
     int lane_blocks = 0;
-    {
+    if (!block_form) {
         ffm::CoreStepArgs a{};
         a.H = H; a.W = W; a.A = e->d.agent_capacity; a.F = fmax; a.auto_reset = e->d.auto_reset;
         a.envp = d_envp; a.rooms = d_rooms; a.room_of_env = d_roe;   // the occupancy of the room form
@@ -1392,10 +1415,28 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     e->room_stride = lay.stride;
     e->room_fmax = fmax;
     e->room_lane_blocks = lane_blocks;
+    e->room_block = block_form;
     e->room_maps.assign(maps, maps + (size_t)n_rooms * HW);
     e->room_sffs.assign(sffs, sffs + (size_t)n_rooms * HW);
     e->room_of_env.assign(room_of_env, room_of_env + E);
     e->room_f = std::move(room_f);
+    return FFM_OK;
+}
+
+int ffm_engine_set_env_rooms_kernel(ffm_engine* e, int32_t mode) {
+    if (!e) return fail(FFM_E_INVALID, "null engine");
+    if (mode != 0 && mode != 1) return fail(FFM_E_INVALID, "env rooms kernel: mode must be 0 (lane) or 1 (block)");
+    if (rooms_on(e)) return fail(FFM_E_INVALID, "env rooms kernel: rooms are on (turn them off first)");
+    if (mode == 1) {
+        if (e->mt) return fail(FFM_E_UNSUPPORTED, "env rooms kernel: Philox engines only");
+        if (e->f64) return fail(FFM_E_UNSUPPORTED, "env rooms kernel: float32-SFF engines only");
+        if (e->lane || e->group)
+            return fail(FFM_E_UNSUPPORTED, "env rooms kernel: lane and group engines have the lane kernel's room form");
+        if (e->big)
+            return fail(FFM_E_UNSUPPORTED, "env rooms kernel: engines with their state in global scratch (block_scratch) "
+                                           "have no room form (u16 free lists, state outside the LDS)");
+    }
+    e->room_kernel = mode;
     return FFM_OK;
 }
 

@@ -83,7 +83,7 @@ struct CoreStepArgs {
     // Per-env rooms (ffm_engine_set_env_rooms): the room table (one record of room_stride bytes per
     // room, room_layout below) and the [E] room index of every env, or nullptr (off: pmap, psff and
     // the free lists above hold for every env).  While set, envp is set too, F above is the largest
-    // room's (the LDS sizes) and the launchers pick the lane and reset kernels' ROOM instantiations.
+    // room's (the LDS sizes) and the launchers pick the lane, block and reset kernels' ROOM instantiations.
     const unsigned char* rooms;
     const int* room_of_env;
     int room_stride;
@@ -162,6 +162,8 @@ hipError_t launch_update_dff_env(const float* src, float* dst, long long E, int 
                                  const EnvParams* envp, hipStream_t s);
 // extra LDS of the block kernel's PEP form (the K staged records)
 size_t core_block_pep_smem_bytes(int K);
+// ... and of its room form (the K records and the K room indices)
+size_t core_block_room_smem_bytes(int K);
 // mask: nullptr = every selected env; else ([E] device bytes) only those with a nonzero byte
 hipError_t launch_core_capture_init(const CoreStepArgs& a, const CoreCapture& c, hipStream_t s,
                                     const uint8_t* mask = nullptr);

@@ -32,7 +32,7 @@ EXPORTED = [
     "ffm_engine_set_episode_log", "ffm_engine_drain_episodes", "ffm_engine_get_episode_stats",
     "ffm_debug_stage_image", "ffm_debug_reset_candidates",
     "ffm_engine_set_env_params", "ffm_engine_get_env_params", "ffm_engine_set_env_params_kernel",
-    "ffm_engine_set_env_rooms", "ffm_engine_get_env_rooms",
+    "ffm_engine_set_env_rooms", "ffm_engine_get_env_rooms", "ffm_engine_set_env_rooms_kernel",
     "ffm_learner_create", "ffm_learner_destroy", "ffm_learner_reset", "ffm_learner_reset_envs", "ffm_learner_step",
     "ffm_learner_set_state", "ffm_learner_get_state", "ffm_learner_get_episodes",
     "ffm_learner_set_mt_state", "ffm_learner_get_mt_state", "ffm_learner_get_counters",
@@ -155,6 +155,7 @@ def load_library():
     L.ffm_engine_set_env_params_kernel.argtypes = [P, i32]
     L.ffm_engine_set_env_rooms.argtypes = [P, P, P, i32, P, P]
     L.ffm_engine_get_env_rooms.argtypes = [P, P, P, i32, C.POINTER(i32), P]
+    L.ffm_engine_set_env_rooms_kernel.argtypes = [P, i32]
     L.ffm_np_expf_device.argtypes = [P, P, i64, P]
     L.ffm_debug_stage_image.argtypes = [P, P, i64, C.POINTER(i64)]
     L.ffm_debug_reset_candidates.argtypes = [P, C.POINTER(i32), C.POINTER(C.c_uint32)]
@@ -452,7 +453,9 @@ class Engine:
         return [{k: getattr(q, k) for k in ENV_PARAM_KEYS} for q in arr], soe
 
     # -- per-env rooms -----------------------------------------------------------
-    def set_env_rooms(self, rooms, room_of_env=None, stream=None):
+    _ENV_ROOMS_KERNELS = {"lane": 0, "block": 1}
+
+    def set_env_rooms(self, rooms, room_of_env=None, stream=None, kernel=None):
         """A geometry sweep in one engine (ffm_engine_set_env_rooms): env e runs in
         rooms[room_of_env[e]] and evolves bit for bit like the env with the same global id of an
         engine created with that room's map and SFF.  `rooms`: a sequence of (map, sff) array
@@ -461,11 +464,24 @@ class Engine:
         the envs whose room changed before stepping them: reset(), or reset_envs() over them.
         rooms=None or []: off -- back to the create-time room, kernel and launch geometry.  While
         on the engine steps with the lane kernel's room form, one launch per step
-        (launch_info()); it composes with set_env_params() in either order.  Lane and 12x12 group
-        engines only: MT, float64-SFF, wave and block engines raise NotImplementedError."""
+        (launch_info()); it composes with set_env_params() in either order.  As it stands, lane
+        and 12x12 group engines only: MT, float64-SFF, wave and block engines raise
+        NotImplementedError.
+
+        `kernel`: "lane", "block" or None (the engine's setting, "lane" at create, stays); sticky
+        (ffm_engine_set_env_rooms_kernel).  "block" is the block kernel's room form, for "wave"
+        and "block" engines (rooms beyond the lane kernel's shapes): while on the engine steps with
+        the block kernel.  On lane, group, MT, float64-SFF and "block_scratch" engines it raises
+        NotImplementedError; changing the kernel while rooms are on raises ValueError (turn them
+        off first).  A failed call changes nothing, the setting included."""
+        if kernel is not None and kernel not in self._ENV_ROOMS_KERNELS:
+            raise ValueError(f"kernel must be None, 'lane' or 'block', got {kernel!r}")
         rooms = list(rooms) if rooms is not None else []
         if not rooms:
             _check(self._L.ffm_engine_set_env_rooms(self._h, None, None, 0, None, _stream_handle(stream)))
+            if kernel is not None:
+                _check(self._L.ffm_engine_set_env_rooms_kernel(self._h, self._ENV_ROOMS_KERNELS[kernel]))
+                self._env_rooms_kernel = kernel
             return
         maps = np.empty((len(rooms), self.H, self.W), np.uint8)
         sffs = np.empty((len(rooms), self.H, self.W), np.float32)
@@ -482,8 +498,20 @@ class Engine:
             roe = np.ascontiguousarray(room_of_env, dtype=np.int32).reshape(-1)
             if roe.size != self.n_envs:
                 raise ValueError(f"room_of_env must have n_envs = {self.n_envs} entries, got {roe.size}")
-        _check(self._L.ffm_engine_set_env_rooms(self._h, _ptr(maps), _ptr(sffs), len(rooms), _ptr(roe),
-                                                _stream_handle(stream)))
+        # the kernel first (a refusal leaves everything as it was); bad tables then put it back
+        before = getattr(self, "_env_rooms_kernel", "lane")
+        changed = kernel is not None and kernel != before
+        if changed:
+            _check(self._L.ffm_engine_set_env_rooms_kernel(self._h, self._ENV_ROOMS_KERNELS[kernel]))
+        try:
+            _check(self._L.ffm_engine_set_env_rooms(self._h, _ptr(maps), _ptr(sffs), len(rooms), _ptr(roe),
+                                                    _stream_handle(stream)))
+        except Exception:
+            if changed:
+                self._L.ffm_engine_set_env_rooms_kernel(self._h, self._ENV_ROOMS_KERNELS[before])
+            raise
+        if changed:
+            self._env_rooms_kernel = kernel
 
     def env_rooms(self):
         """(maps [R, H, W] uint8, sffs [R, H, W] float32, room_of_env [n_envs] int32) in effect
@@ -716,7 +744,8 @@ class Engine:
         env shards a step(n > 1) call runs as under the current settings (1 = one launch per step
         over all envs) with the blocks of one shard's grid, and whether those launches take the
         group kernel's single-group form ("group_one"; False: its loop form, or another kernel).
-        "env_rooms": the room count of set_env_rooms(), 0 while off (on: the lane kernel, one shard)."""
+        "env_rooms": the room count of set_env_rooms(), 0 while off (on: the lane kernel, or with
+        kernel="block" the block kernel; one shard)."""
         v = np.zeros(10, np.int32)
         _check(self._L.ffm_debug_launch_info(self._h, _ptr(v), len(v)))
         rooms = C.c_int32()

@@ -33,6 +33,14 @@ index) and, when ``exit_width`` is swept, an ``exit_width`` column.  A room swee
 ``--sweep-kernel {lane,group}`` picks the kernel that steps a sweep in a 12x12 engine (one born on
 the group kernel): the lane kernel's per-env form or the group kernel's own.  The outputs are
 the same bits either way; the default (SWEEP_KERNEL_DEFAULT) is the one that measured faster.
+
+Rooms beyond the lane kernel's shapes (an engine whose kernel is ``wave`` or ``block``, such as the
+reference's 50x50 room) sweep with the block kernel's room form, which the driver picks by itself
+(``room_sweep_kernel``).  ``--sff geodesic`` gives rooms made by ``--room`` the obstacle-aware static
+floor field (``data.geodesic_sff``) instead of the L1 distance; on rooms without obstacles the two
+are the same bits.
+
+    python -m ffm_amd.evac --room 50 50 --N 100 --sweep exit_width=1,2,4 --envs 1024 --out runs/rooms50
 """
 from __future__ import annotations
 
@@ -51,6 +59,38 @@ ROOM_SWEEP_NAMES = ("exit_width",)   # swept through the room axis (--room H W),
 # faster than the lane kernel's in every run at 4,096, 32,768 and 65,536 envs (1.36, 1.64 and 1.66
 # times; profiles/env_params_group/ab.txt).
 SWEEP_KERNEL_DEFAULT = "group"
+
+
+SFF_KINDS = ("l1", "geodesic")          # --sff for rooms made by --room
+
+
+def parse_sff(text, made_room: bool):
+    """The value of ``--sff``: (kind, path).  ``l1`` / ``geodesic`` name the field of a room made by
+    ``--room`` (kind, None); anything else is the .npy file that goes with ``--map`` (None, path).
+    None -> ("l1", None) with ``--room``, else (None, None)."""
+    if text is None:
+        return ("l1", None) if made_room else (None, None)
+    if text in SFF_KINDS:
+        if not made_room:
+            raise ValueError(f"--sff {text} wants --room H W (with --map, --sff is the field's .npy file)")
+        return text, None
+    if made_room:
+        raise ValueError(f"--sff with --room is one of {' '.join(SFF_KINDS)}, got {text!r}")
+    return None, text
+
+
+def room_sff(kind: str, m: np.ndarray, neighborhood: str) -> np.ndarray:
+    """The static floor field of a made room: ``l1`` or ``geodesic`` (the engine's moves)."""
+    from .data import geodesic_sff, l1_sff
+    return l1_sff(m) if kind == "l1" else geodesic_sff(m, neighborhood=neighborhood)
+
+
+def room_sweep_kernel(launch_info: dict):
+    """The ``kernel`` argument of ``Engine.set_env_rooms`` for an engine with this ``launch_info()``:
+    "block" where the create-time kernel is ``wave`` or ``block`` (the block kernel's room form),
+    None elsewhere (lane and group engines have the lane form; a ``block_scratch`` engine has none
+    and keeps the refusal of a plain call)."""
+    return "block" if launch_info.get("kernel") in ("wave", "block") else None
 
 
 def parse_sweep(text: str):
@@ -164,7 +204,8 @@ def summary_text(steps: np.ndarray, total_steps: int, seconds: float) -> str:
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--map", help=".npy map (0 free, 2 wall, 3 exit)")
-    ap.add_argument("--sff", help=".npy static floor field of the map")
+    ap.add_argument("--sff", help=".npy static floor field of the map; with --room: l1 (default) or geodesic "
+                                  "(obstacle-aware, data.geodesic_sff)")
     ap.add_argument("--room", nargs=2, type=int, metavar=("H", "W"), help="a walled H x W room with one exit")
     ap.add_argument("--rooms", nargs="+", metavar="MAP.npy:SFF.npy",
                     help="several rooms of one shape in one engine (the room axis of the sweep)")
@@ -192,10 +233,16 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
-    if bool(a.map) != bool(a.sff) or sum(map(bool, (a.map, a.room, a.rooms))) != 1:
+    if sum(map(bool, (a.map, a.room, a.rooms))) != 1 or (a.rooms and a.sff):
+        ap.error("give either --map and --sff, or --room H W, or --rooms MAP.npy:SFF.npy ...")
+    try:
+        sff_kind, sff_path = parse_sff(a.sff, bool(a.room))
+    except ValueError as err:
+        ap.error(str(err))
+    if bool(a.map) != bool(sff_path):
         ap.error("give either --map and --sff, or --room H W, or --rooms MAP.npy:SFF.npy ...")
 
-    from .data import l1_sff, make_room
+    from .data import make_room
     from .engine import Engine
     params = {"k_S": a.k_S, "k_D": a.k_D, "diffuse": a.diffuse, "decay": a.decay, "neighborhood": a.neighborhood}
     rooms = widths = None      # the room axis: (map, sff) pairs, and the exit widths that made them
@@ -212,7 +259,7 @@ def main(argv=None):
         if room_sweeps:
             widths = room_sweeps[0][1]
             maps = [make_room(*a.room, exit_pos=(0, a.room[1] // 2), exit_width=w) for w in widths]
-            rooms = [(mp, l1_sff(mp)) for mp in maps]
+            rooms = [(mp, room_sff(sff_kind, mp, a.neighborhood)) for mp in maps]
         elif a.rooms:
             rooms = []
             for text in a.rooms:
@@ -224,9 +271,9 @@ def main(argv=None):
             m, sff = rooms[0]
         elif a.room:
             m = make_room(*a.room)
-            sff = l1_sff(m)
+            sff = room_sff(sff_kind, m, a.neighborhood)
         else:
-            m, sff = np.load(a.map), np.load(a.sff)
+            m, sff = np.load(a.map), np.load(sff_path)
         if sweeps or rooms:
             sets = sweep_grid(sweeps, {**params, "N": a.N}, len(rooms) if rooms else 0, widths)
             soe = env_assignment(a.envs, len(sets))
@@ -237,7 +284,8 @@ def main(argv=None):
                  auto_reset=a.episodes > 1)
     try:   # before the reset: its placement takes each env's own room and N
         if rooms:
-            eng.set_env_rooms(rooms, np.array([sets[p]["room"] for p in soe], np.int32))
+            eng.set_env_rooms(rooms, np.array([sets[p]["room"] for p in soe], np.int32),
+                              kernel=room_sweep_kernel(eng.launch_info()))
         if sets and (sweeps or not rooms):
             # the room axis is the slowest: combination c has the parameters of combination c % Pp
             n_par = len(sets) // max(1, len(rooms) if rooms else 1)

@@ -307,7 +307,9 @@ int ffm_engine_set_env_params_kernel(ffm_engine* eng, int32_t mode);
  * engines, and engines on which the lane kernel cannot run (agent_capacity > 32, W % 4 != 0,
  * H*W > 256, or its LDS at the largest room's free-cell count beyond 64 KB).
  *
- * Scope: 12x12 group engines and lane engines.  Wave and block engines have no room form yet.
+ * Scope: 12x12 group engines and lane engines.  Wave and block engines take the block kernel's
+ * room form, which is opt-in: ffm_engine_set_env_rooms_kernel(eng, 1) below.  Without it this
+ * call refuses them as above.
  *
  * May be called between steps; stream-ordered on `stream`, which it synchronises: the tables are
  * consumed before it returns.  The room holds from the next launch.  An env whose room changes
@@ -323,7 +325,8 @@ int ffm_engine_set_env_params_kernel(ffm_engine* eng, int32_t mode);
  * room's free-cell count by the expression create uses (FFM_RESET_CANDIDATES is honoured).
  * Turning either feature off rebuilds what the other needs.
  *
- * Kernel: while rooms are on the engine steps with the lane kernel's room form, one launch per
+ * Kernel: while rooms are on the engine steps with the lane kernel's room form (or the block
+ * kernel's: ffm_engine_set_env_rooms_kernel), one launch per
  * step: step shards and fused steps are off (ffm_engine_set_fused_steps(k > 1) is accepted and
  * ignored meanwhile, as under trajectory capture), and a sticky
  * ffm_engine_set_env_params_kernel(eng, 1) is remembered and resumes when rooms are turned off.
@@ -336,6 +339,28 @@ int ffm_engine_set_env_rooms(ffm_engine* eng, const uint8_t* maps, const float* 
  * cap < *n_rooms: FFM_E_INVALID with *n_rooms = the count needed. */
 int ffm_engine_get_env_rooms(ffm_engine* eng, uint8_t* maps, float* sffs, int32_t cap, int32_t* n_rooms,
                              int32_t* room_of_env);
+/* The kernel that steps the engine while rooms are on: mode 0 = lane (the create-time default:
+ * ffm_engine_set_env_rooms behaves as described above), mode 1 = block -- the block kernel's room
+ * form, for rooms beyond the lane kernel's shapes (the reference's 50x50 room, 64x64 with hundreds
+ * of agents).  Sticky: read by the next ffm_engine_set_env_rooms.  FFM_E_INVALID: another value,
+ * or rooms are on (turn them off first).
+ *
+ * Mode 1 is accepted on Philox, float32-SFF engines whose create-time kernel is the wave or the
+ * block kernel.  FFM_E_UNSUPPORTED, nothing changed: lane and group engines (they have the lane
+ * form), MT and float64-SFF engines, and engines whose block kernel keeps its state in a global
+ * scratch region (maps beyond the LDS, `block_scratch`): their padded cell indices do not fit the
+ * room table's u16 free lists, and their grid and tile live outside the LDS the room form fills.
+ *
+ * With mode 1 set, ffm_engine_set_env_rooms validates as above (everything before anything
+ * changes), builds the same room table and per-env records, and instead of the lane kernel's
+ * conditions checks the block kernel's: its LDS at the create-time K (envs per workgroup) with the
+ * largest room's free-cell count plus K * 36 bytes (the K records and room indices), the
+ * placement's room for the largest free list, and the counter slots; FFM_E_UNSUPPORTED with
+ * nothing changed if one fails.  While on, the engine steps with the block kernel (a wave engine
+ * moves to it, as under ffm_engine_set_env_params), fused steps do not apply, and everything
+ * said above about composition, resets, the log, capture and update_dff holds.  n_rooms = 0
+ * restores the create-time kernel and grid. */
+int ffm_engine_set_env_rooms_kernel(ffm_engine* eng, int32_t mode);
 
 /* counters[4] = {agent_steps, exits, resets, steps} accumulated since create. */
 int ffm_engine_get_counters(ffm_engine* eng, uint64_t* counters, void* stream);
