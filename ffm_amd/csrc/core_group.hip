@@ -99,6 +99,35 @@ __host__ __device__ inline size_t group_shared_bytes(int PHW, int F) {
 // in the image in global memory.
 __host__ __device__ inline size_t group_one_shared_bytes(int PHW) { return a16((size_t)PHW * 4); }
 
+// The room form's carve (per-env rooms, core_group_kernel<.., ROOM>).  No block-shared region: the
+// wave holds every env's own grid (stride room_layout().gs codes) and, in the FFM_GROUP_ROOM_SFF_LDS=1
+// build, its raw SFF (stride ss floats), so each is copied from the room table in whole 16-byte words.  The placement keys reuse the grids and
+// tiles (dead past the stencil) and are sized by F, the largest room's count.  The form is built on
+// the single-group form without a kept-prefix array (FFM_GROUP_FIT >= 1) and never defers a placement.
+struct GroupRoomCarve {
+    GroupCarve c;
+    size_t sff;
+};
+// SFFLDS false (the product build): no SFFs in LDS; decide reads them from the table.
+template <int G, bool SFFLDS = true>
+__host__ __device__ inline GroupRoomCarve group_room_carve(int PHW, int TS, int F) {
+    const RoomLayout lay = room_layout(PHW, F);
+    GroupRoomCarve r;
+    size_t o = 0;
+    r.c.grid = o;  o += a16((size_t)G * lay.gs * 2);
+    r.c.tile = o;  o += a16((size_t)G * TS * 4);
+    r.c.keys = 0;
+    const size_t keys_end = a16((size_t)(F > 0 ? F : 1) * 8);
+    if (o < keys_end) o = keys_end;
+    r.sff = o;     o += SFFLDS ? a16((size_t)G * lay.ss * 4) : 0;
+    r.c.words = o; o += (size_t)G * 32 * 4;
+    r.c.posst = o; o += a16((size_t)G * 16 * 4);   // the group's position dwords (A <= 32)
+    r.c.kp = r.c.pend = o;                         // neither exists in this carve
+    r.c.dummy = o; o += 4;
+    r.c.per_wave = a16(o);
+    return r;
+}
+
 // The stage image (CoreStepArgs::stage): the block-shared region above byte for byte (pads zero),
 // then one table per group size of the per-lane slot geometry, which depends on (G, lane) only.
 // A table is three arrays of 64 uint4, one entry per lane each (a 16-byte load):
@@ -172,11 +201,14 @@ __device__ __forceinline__ float lane_f32(float x, int l) {
 // control flow with all lanes active; csv is the chunk's cs word, wx / wy the decide draw.
 // PEP: psff is the raw SFF, and lane s < G of kSv / kDv holds env s's f32(-k_S) / f32(k_D); the
 // pending agent's env is wave-uniform here, so its two values are one readlane each.
-template <int W, int PHW, int TS, bool PEP = false>
+// SSE > 0 (the room form): psff holds one raw SFF per env of the group, SSE floats apart, and PHW is
+// the grids' stride.  SSE < 0 (the room form reading the SFF from the room table): psff is room 0's
+// SFF in the table, lane s < G of roomv holds env s's room index and rstride is the record stride in floats.
+template <int W, int PHW, int TS, bool PEP = false, int SSE = 0>
 __device__ __forceinline__ uint32_t group_exact_coop(unsigned long long pend, uint32_t slot, uint32_t csv, uint32_t wx,
                                                      uint32_t wy, const uint16_t* grid, const float* psff,
                                                      const float* tile, float kD, int lane, float kSv = 0.0f,
-                                                     float kDv = 0.0f) {
+                                                     float kDv = 0.0f, int roomv = 0, int rstride = 0) {
     constexpr int NB = 4, PW = W + 2;
     while (pend) {
         const int L = __builtin_ctzll(pend);   // lowest pending lane first
@@ -194,7 +226,9 @@ __device__ __forceinline__ uint32_t group_exact_coop(unsigned long long pend, ui
         const uint32_t g = grid[s * PHW + cell];
         // the valid candidates as a wave-uniform mask: free or exit neighbours, and the stay
         const unsigned vm = ((unsigned)__ballot(g == 0u || g == 3u) & ((1u << NB) - 1u)) | (1u << NB);   // :52-60
-        const float sa = PEP ? lane_f32(kSv, s) * psff[cell] : psff[cell];
+        const float* sf = psff + (SSE > 0 ? s * SSE : 0);
+        if constexpr (SSE < 0) sf = psff + (size_t)__builtin_amdgcn_readlane(roomv, s) * (size_t)rstride;
+        const float sa = PEP ? lane_f32(kSv, s) * sf[cell] : psff[cell];
         const float sb = (PEP ? lane_f32(kDv, s) : kD) * tile[s * TS + pp + dd0 + doff];
         const float sc = sa + sb;                                                      // :77
         float mx = -__builtin_inff();
@@ -313,6 +347,16 @@ constexpr bool kGroupFitCarve = FFM_GROUP_FIT >= 3;
 #define FFM_GROUP_PEP_BPERMUTE 1
 #endif
 
+// The room form's SFFs (per-env rooms).  0, the product build: they stay in the room table and decide
+// reads the agent's env's room's SFF there, through L1 / L2 (a few rooms of 784 bytes each).  1 (an A/B
+// build) copies every env's raw SFF into the wave's LDS first: 3.1 KB more per wave at G = 4, 33.3 KB
+// per block and four blocks per CU instead of seven, and 30.85 against 23.07 us per step at 65,536
+// envs (slower at every size measured: profiles/env_rooms_group/ab.txt).
+#ifndef FFM_GROUP_ROOM_SFF_LDS
+#define FFM_GROUP_ROOM_SFF_LDS 0
+#endif
+constexpr bool kRoomSffLds = FFM_GROUP_ROOM_SFF_LDS != 0;
+
 #ifndef FFM_GROUP_G
 #define FFM_GROUP_G 4
 #endif
@@ -336,7 +380,16 @@ constexpr int kGroupGSmall = FFM_GROUP_G_SMALL;   // envs per group when the lar
 // the group's state; decide takes the agent's env's kS32 / kD32 on the raw SFF (a.stage is then the
 // image built with multiplier 1), the stencil the c0 / c1 of each slot's env, the count store and
 // the placements the env's N.  No KD1 variant: k_D * DFF with k_D == 1 is DFF exactly.
-template <int NB, int HT, int WT, int G, bool KD1, bool EPL, bool ONE, bool PEP = false>
+// ROOM (only with ONE and PEP): per-env rooms (a.rooms / a.room_of_env, kernels.h).  Lane s < G holds
+// env s's room index, loaded with the group's state (a partial last group reads 0: room 0, always
+// valid).  There is no block-shared region and no __syncthreads: the wave copies each env's grid codes
+// from its room's record of the table into its own LDS (group_room_carve; 16-byte loads spread over
+// the lanes, L2-resident), decide reads the agent's env's grid there and its room's raw SFF in the
+// table (FFM_GROUP_ROOM_SFF_LDS=1: from a copy in LDS), and a placement takes the env's room's free
+// list and F straight from the record.  Every index into a grid, an SFF
+// or a tile comes from a position (< H * W) or a host-validated free-list entry, none from a map
+// code: an env stepped in a room it was not placed in stays memory-safe (undefined for that env only).
+template <int NB, int HT, int WT, int G, bool KD1, bool EPL, bool ONE, bool PEP = false, bool ROOM = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ONE ? FFM_GROUP_ONE_WAVES : FFM_GROUP_WAVES, 8)))
 void core_group_kernel(CoreStepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -354,16 +407,28 @@ void core_group_kernel(CoreStepArgs a) {
     constexpr int PWORDS = G * 16;             // position dwords per group (A <= 32)
     static_assert(G >= 1 && G <= 8 && HW % 4 == 0 && H + 1 < 128, "group geometry");
     static_assert(!PEP || !KD1, "the per-env form multiplies by every env's own k_D");
+    static_assert(!ROOM || (PEP && ONE), "the room form takes every env's record and is built on the single-group form");
+    // the room form: grids and SFFs strided per env as in the room table (whole 16-byte words)
+    constexpr int GS = ROOM ? ((PHW + 7) & ~7) : PHW, SS = (PHW + 3) & ~3;
     static_assert(MAXC * 64 >= G * 32 && PWORDS * 4 <= (MAXC * 64 + 1) * 2, "kp spans the chunks; posst fits in it");
     // what the single-group form does without, by FFM_GROUP_FIT
     constexpr bool NOKP = ONE && FFM_GROUP_FIT >= 1, NOPOS = ONE && FFM_GROUP_FIT >= 2, FITC = ONE && kGroupFitCarve;
     static_assert(!NOPOS || PWORDS <= 64, "the group's positions are one dword per lane");
     static_assert(!NOKP || MAXC <= 2, "the kept prefixes are read from the first or the last chunk");
+    static_assert(!ROOM || (NOKP && !NOPOS && !FITC), "the room form's carve: staged positions, no kept-prefix array");
     const int A = a.A;
     const int lane = (int)(threadIdx.x & 63);
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 
-    const GroupCarve cv = group_carve<G, FITC>(PHW, TS, a.F);
+    size_t room_sff = 0;   // ROOM: the SFFs' offset in the wave's carve
+    const GroupCarve cv = [&] {
+        if constexpr (ROOM) {
+            const GroupRoomCarve rc = group_room_carve<G, kRoomSffLds>(PHW, TS, a.F);
+            room_sff = rc.sff;
+            return rc.c;
+        } else
+            return group_carve<G, FITC>(PHW, TS, a.F);
+    }();
     // block-shared (group_shared_bytes): the map and the widened map are in the image too, but
     // the kernel reads only the SFF term and the free list from LDS.  FITC: the SFF term alone
     // (group_one_shared_bytes), and the free list is read where it lies in the image.
@@ -371,8 +436,10 @@ void core_group_kernel(CoreStepArgs a) {
     const float* psff = reinterpret_cast<const float*>(smem + (FITC ? 0 : kImgSff));
     const uint16_t* pfree = FITC ? reinterpret_cast<const uint16_t*>(static_cast<const unsigned char*>(a.stage) + kImgFree)
                                  : reinterpret_cast<const uint16_t*>(smem + kImgFree);
-    unsigned char* wbase = smem + (FITC ? group_one_shared_bytes(PHW) : group_shared_bytes(PHW, a.F)) +
+    unsigned char* wbase = smem + (ROOM ? 0 : FITC ? group_one_shared_bytes(PHW) : group_shared_bytes(PHW, a.F)) +
                            (size_t)wv * cv.per_wave;
+    // ROOM: psff and pfree above are not read; FFM_GROUP_ROOM_SFF_LDS=1: the group's SFFs, env s at sffw + s * SS
+    const float* const sffw = ROOM ? reinterpret_cast<const float*>(wbase + room_sff) : psff;
     uint16_t* const grid = reinterpret_cast<uint16_t*>(wbase + cv.grid);
     float* const tile = reinterpret_cast<float*>(wbase + cv.tile);
     uint32_t* const words = reinterpret_cast<uint32_t*>(wbase + cv.words);
@@ -492,7 +559,13 @@ void core_group_kernel(CoreStepArgs a) {
     // PEP: the placement of env e of this launch with its own N and threshold, read here: rare,
     // nothing of the step is live
     auto place = [&](long long e) {
-        if constexpr (PEP)
+        if constexpr (ROOM) {   // ... and its own room's free list and F, from the table (keys holds a.F pairs)
+            const unsigned char* rec = a.rooms + (size_t)a.room_of_env[e] * (size_t)a.room_stride;
+            wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys,
+                                     reinterpret_cast<const uint16_t*>(rec + room_layout(PHW, a.F).free),
+                                     a.pos + e * A, lane, a.envp[e].N, a.envp[e].reset_thr,
+                                     min(*reinterpret_cast<const int*>(rec), a.F));
+        } else if constexpr (PEP)
             wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane, a.envp[e].N,
                                      a.envp[e].reset_thr);
         else wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane);
@@ -508,7 +581,44 @@ void core_group_kernel(CoreStepArgs a) {
     if (!ONE) load(g < ngroups ? g : -1, cur);
     else if (g < ngroups) load(g, cur);   // wave-uniform; cur is read under the same guard only
 
-    if (LAD >= 1) {
+    int roomv = 0;   // ROOM, lane s < G: env s's room index
+    if constexpr (ROOM) {
+        if (LAD >= 1 && g < ngroups) {   // wave-uniform: a wave without a group stages nothing
+            // lane s < G: env s's room index.  One resource over the launch's E indices with the
+            // group's base as the scalar offset: past the last env the load returns 0, room 0.
+            roomv = (int)__builtin_amdgcn_raw_buffer_load_b32(pair_rsrc(a.room_of_env, (int)E * 4),
+                                                                        lane < G ? lane * 4 : kOOB, g * G * 4, 0);
+            // Every env's grid codes and raw SFF from its room's record (the host checked every index
+            // and that room_stride is room_layout()'s): 16-byte word q of the G grids is word q % GQ of
+            // env q / GQ's, and lands at byte 16 q of the wave's grids, whose stride is the record's.
+            const RoomLayout lay = room_layout(PHW, a.F);
+            constexpr int GQ = GS * 2 / 16, SQ = SS * 4 / 16;
+            static_assert((GS * 2) % 16 == 0 && (SS * 4) % 16 == 0, "whole 16-byte words per env");
+            // env s's index from the lane that holds it, taken with every lane active (s < G always)
+            auto room_of = [&](int s, int bit) {
+                const int r = __builtin_amdgcn_ds_bpermute(s * 4, roomv);
+                return (FFM_GROUP_ABLATE & bit) ? __builtin_amdgcn_readlane(roomv, 0) : r;   // diagnostic: env 0's room for all
+            };
+#pragma unroll
+            for (int q0 = 0; q0 < G * GQ; q0 += 64) {
+                const int q = q0 + lane, s = min(q / GQ, G - 1);
+                const unsigned char* rec = a.rooms + (size_t)room_of(s, 4) * (size_t)a.room_stride;
+                if (q < G * GQ)
+                    reinterpret_cast<uint4*>(grid)[q] = reinterpret_cast<const uint4*>(rec + lay.grid)[q - s * GQ];
+            }
+#pragma unroll
+            for (int q0 = 0; q0 < (kRoomSffLds ? G * SQ : 0); q0 += 64) {
+                const int q = q0 + lane, s = min(q / SQ, G - 1);
+                const unsigned char* rec = a.rooms + (size_t)room_of(s, 2) * (size_t)a.room_stride;
+                if (q < G * SQ)
+                    reinterpret_cast<uint4*>(wbase + room_sff)[q] = reinterpret_cast<const uint4*>(rec + lay.sff)[q - s * SQ];
+            }
+            // the tiles' halos, as below
+            if ((geo >> 24) != 255u) reinterpret_cast<float4*>(tile)[geo >> 24] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        // the wave's own grids, SFFs and halos before its mark and decide read them: no block-wide barrier
+        if (LAD >= 1) wave_sync();
+    } else if (LAD >= 1) {
     // Block-shared region: the image's first sq4 float4s, one 16-byte load and LDS store per
     // thread (the host checks sq4 <= 256).  The map, f32(-k_S) * SFF, the free list and the
     // widened map are engine constants: nothing is recomputed per launch.
@@ -625,7 +735,7 @@ void core_group_kernel(CoreStepArgs a) {
                 const int x = (int)__umulhi(p, mW);
                 const int y = (int)p - x * W;
                 const int pp = live ? (x + 1) * PW + y + 1 : PW + 1;
-                grid[live ? s * PHW + pp : kDummy16] = (uint16_t)(DirCodes::kAgent | (uint32_t)al | (DirCodes::kNoDir << 8));
+                grid[live ? s * GS + pp : kDummy16] = (uint16_t)(DirCodes::kAgent | (uint32_t)al | (DirCodes::kNoDir << 8));
                 cs[c] = (uint32_t)pp | ((uint32_t)al << 16) | ((uint32_t)s << 21) | ((live ? 1u : 0u) << 24) |
                         ((uint32_t)(live ? x + 1 : 1) << 25);
             }
@@ -644,32 +754,48 @@ void core_group_kernel(CoreStepArgs a) {
                 const uint32_t genv = ebase + (uint32_t)e0 + (uint32_t)s;
                 const uint4 pb = philox(make_uint4(a.t, genv, (uint32_t)al, kPurDecide << 28), a.key0, a.key1);
                 words[live ? s * 32 + al : kDummy32] = pb.w;   // the friction draw, if this agent owns a contested target
-                const uint16_t* gk = grid + s * PHW;
+                const uint16_t* gk = grid + s * GS;
                 const float* dk = tile + s * TS;
                 const int dd0 = 3 - 2 * cs_xp1(v);
                 bool to_exit = false;
+                // ROOM: the agent's env's own SFF (idle lanes: env 0's)
+                const float* sk = psff;
+                if constexpr (ROOM) {
+                    if (kRoomSffLds) sk = sffw + s * SS;
+                    else {   // the agent's env's room's SFF where it lies in the table (every lane is active here)
+                        const int r = (FFM_GROUP_ABLATE & 2) ? __builtin_amdgcn_readlane(roomv, 0)
+                                                             : __builtin_amdgcn_ds_bpermute(s * 4, roomv);
+                        sk = reinterpret_cast<const float*>(a.rooms + (size_t)r * (size_t)a.room_stride +
+                                                            room_layout(PHW, a.F).sff);
+                    }
+                }
                 // PEP: the agent's env's k_S / k_D (idle lanes: env 0's), on the raw SFF
                 float kSe = a.kS32, kDe = a.kD32;
                 if constexpr (PEP) {
                     kSe = env_val(cur.pr.x, s);
                     kDe = env_val(cur.pr.y, s);
                 }
-                uint32_t slot = PEP ? lane_decide<NB, false, false>(pp, PW, gk, psff, dk, dd0, kSe, kDe, pb.x, to_exit)
+                uint32_t slot = PEP ? lane_decide<NB, false, false>(pp, PW, gk, sk, dk, dd0, kSe, kDe, pb.x, to_exit)
                                     : lane_decide<NB, true, KD1>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32, pb.x, to_exit);
                 slot = live ? slot : kNoReq;
                 // u near a cdf boundary: the exact NumPy arithmetic decides
                 if (NB == 4 && FFM_GROUP_COOP_EXACT) {
                     const unsigned long long pm = __ballot(slot == kPending);
                     if (pm)   // wave-uniform, rare
-                        slot = PEP ? group_exact_coop<W, PHW, TS, true>(pm, slot, v, pb.x, pb.y, grid, psff, tile, 0.0f,
-                                                                        lane, cur.pr.x, cur.pr.y)
-                                   : group_exact_coop<W, PHW, TS>(pm, slot, v, pb.x, pb.y, grid, psff, tile, a.kD32, lane);
+                        slot = !PEP ? group_exact_coop<W, PHW, TS>(pm, slot, v, pb.x, pb.y, grid, psff, tile, a.kD32, lane)
+                               : ROOM && !kRoomSffLds
+                                   ? group_exact_coop<W, GS, TS, true, -1>(
+                                         pm, slot, v, pb.x, pb.y, grid,
+                                         reinterpret_cast<const float*>(a.rooms + room_layout(PHW, a.F).sff), tile, 0.0f,
+                                         lane, cur.pr.x, cur.pr.y, roomv, a.room_stride / 4)
+                                   : group_exact_coop<W, GS, TS, true, ROOM ? SS : 0>(pm, slot, v, pb.x, pb.y, grid, sffw, tile,
+                                                                                      0.0f, lane, cur.pr.x, cur.pr.y);
                 } else if (slot == kPending)
-                    slot = NB == 4 ? lane_decide_exact<NB, !PEP>(pp, PW, gk, psff, dk, dd0, kSe, kDe, u53(pb.x, pb.y))
-                                   : lane_decide_exact_arr<NB, !PEP>(pp, PW, gk, psff, dk, dd0, kSe, kDe,
+                    slot = NB == 4 ? lane_decide_exact<NB, !PEP>(pp, PW, gk, sk, dk, dd0, kSe, kDe, u53(pb.x, pb.y))
+                                   : lane_decide_exact_arr<NB, !PEP>(pp, PW, gk, sk, dk, dd0, kSe, kDe,
                                                                      u53(pb.x, pb.y));
                 const uint32_t sd = slot <= (uint32_t)NB ? slot : DirCodes::kNoDir;
-                grid[live ? s * PHW + pp : kDummy16] =
+                grid[live ? s * GS + pp : kDummy16] =
                     (uint16_t)(DirCodes::kAgent | (uint32_t)al | (sd << 8) | ((pb.z >> 31) << 12));
                 cr[c] = sd | ((to_exit ? 1u : 0u) << 4);
 #if FFM_GROUP_PROBE_DUP
@@ -702,7 +828,7 @@ void core_group_kernel(CoreStepArgs a) {
                 const uint32_t sd = cr[c] & 15u;
                 const bool to_exit = (cr[c] & 16u) != 0u;
                 const uint32_t slot = sd == DirCodes::kNoDir ? (uint32_t)kNoReq : sd;
-                const uint16_t* gk = grid + s * PHW;
+                const uint16_t* gk = grid + s * GS;
                 const int r = (int)slot_cell_k<NB, PW>(slot, pp);
                 const bool req = slot <= (uint32_t)NB;
                 const bool moving = req && r != pp;
@@ -750,7 +876,7 @@ void core_group_kernel(CoreStepArgs a) {
             if (c * 64 < T) {
                 const uint32_t v = cs[c];
                 if (!NOKP) kp[c * 64 + lane] = (uint16_t)(cr[c] >> 17);   // idle lanes' entries are never read
-                grid[cs_live(v) ? cs_s(v) * PHW + cs_pp(v) : kDummy16] = 0;   // unmark: agents stand on free cells
+                grid[cs_live(v) ? cs_s(v) * GS + cs_pp(v) : kDummy16] = 0;   // unmark: agents stand on free cells
             }
         }
         if (!NOKP && lane == 0) kp[T] = (uint16_t)kept;
@@ -960,8 +1086,12 @@ void core_group_kernel(CoreStepArgs a) {
 }
 
 // one: the single-group form's own size (its carve and block-shared region, kGroupFitCarve).
-size_t core_group_smem_bytes(int H, int W, int F, int waves, int G, bool one) {
+// room: the room form's (per-env rooms: its own carve, no block-shared region; F the largest room's).
+size_t core_group_smem_bytes(int H, int W, int F, int waves, int G, bool one, bool room) {
     const int PHW = (H + 2) * (W + 2), TS = lane_tile_floats(H, W);
+    if (room)
+        return (size_t)waves * (G == kGroupGSmall ? group_room_carve<kGroupGSmall, kRoomSffLds>(PHW, TS, F).c.per_wave
+                                                  : group_room_carve<kGroupG, kRoomSffLds>(PHW, TS, F).c.per_wave);
     if (one && kGroupFitCarve) {
         const size_t per_wave = G == kGroupGSmall ? group_carve<kGroupGSmall, true>(PHW, TS, F).per_wave
                                                   : group_carve<kGroupG, true>(PHW, TS, F).per_wave;
@@ -1048,8 +1178,32 @@ static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int
     return hipGetLastError();
 }
 
+// The room form (a.rooms set): the single-group form only, so the grid holds a wave per group.
+template <int NB, int G>
+static hipError_t group_room_op(const CoreStepArgs& a, int blocks, hipStream_t s, int op, int* occ) {
+    const size_t smem = core_group_smem_bytes(a.H, a.W, a.F, 4, G, true, true);
+    if (op) {
+        *occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, false, false, true, true, true>,
+                                                         256, smem) != hipSuccess)
+            *occ = 0;
+        return hipSuccess;
+    }
+    if (a.H != 12 || a.W != 12 || a.A > 32 || !a.envp || !a.room_of_env || !a.stage || a.stage_q4 <= 0 ||
+        !core_group_one_group(a.E, blocks, G) || smem > 64 * 1024 ||
+        (size_t)a.room_stride != room_layout((a.H + 2) * (a.W + 2), a.F).stride)
+        return hipErrorInvalidConfiguration;   // shapes, tables and the grid the kernel assumes
+    const dim3 grid((unsigned)blocks), block(256);
+    if (a.ep_start) core_group_kernel<NB, 12, 12, G, false, true, true, true, true><<<grid, block, smem, s>>>(a);
+    else core_group_kernel<NB, 12, 12, G, false, false, true, true, true><<<grid, block, smem, s>>>(a);
+    return hipGetLastError();
+}
+
 template <int NB>
 static hipError_t group_op_kd(const CoreStepArgs& a, int blocks, hipStream_t s, int op, int* occ, int G, bool one) {
+    if (a.rooms)   // per-env rooms: the room form, whatever `one` says (it has no loop form)
+        return G == kGroupGSmall ? group_room_op<NB, kGroupGSmall>(a, blocks, s, op, occ)
+                                 : group_room_op<NB, kGroupG>(a, blocks, s, op, occ);
     if (a.envp)   // per-env parameters: every env's own k_D, so no KD1 variant
         return G == kGroupGSmall ? group_op<NB, false, kGroupGSmall, true>(a, blocks, s, op, occ, one)
                                  : group_op<NB, false, kGroupG, true>(a, blocks, s, op, occ, one);

@@ -121,7 +121,8 @@ struct ffm_engine {
     unsigned char* d_stage_raw = nullptr;      // its stage image: the SFF term with multiplier 1 (the raw SFF);
                                                // built when the feature first moves to the group kernel
     // Per-env rooms (ffm_engine_set_env_rooms): null / empty while off.  While on the engine steps
-    // with the lane kernel's room form, or (room_block) the block kernel's, and d_envp holds a
+    // with the lane kernel's room form, or (room_block) the block kernel's, or (room_group) the group
+    // kernel's, and d_envp holds a
     // record per env: the caller's sets', or (pep_sets empty) the create-time values, each with
     // its room's placement threshold.
     bool lane_ok = false;                      // the lane kernel's conditions hold (create)
@@ -132,6 +133,9 @@ struct ffm_engine {
     int room_lane_blocks = 0;                  // the lane room form's persistent grid
     int room_kernel = 0;                       // ffm_engine_set_env_rooms_kernel's mode (sticky)
     bool room_block = false;                   // rooms are on in the block kernel's form (mode 1)
+    bool room_group = false;                   // rooms are on in the group kernel's form (mode 2)
+    int room_group_blocks = 0, room_group_g = 4;   // its one-launch grid (a wave per group) and envs per group
+    std::vector<Shard> room_shards;            // ... and its step shards (size() <= 1: off)
     std::vector<uint8_t> room_maps;            // the caller's tables, for ffm_engine_get_env_rooms
     std::vector<float> room_sffs;
     std::vector<int32_t> room_of_env;
@@ -145,9 +149,13 @@ static bool pep_on(const ffm_engine* e) { return e->d_envp && !e->pep_sets.empty
 // The kernel that steps the engine under its current settings (per-env parameters move group and
 // wave engines): at most one of these holds, none means the block kernel.
 static bool pep_group_on(const ffm_engine* e) { return !rooms_on(e) && e->d_envp && e->pep_group; }
-static bool steps_group(const ffm_engine* e) { return !rooms_on(e) && e->group && (!e->d_envp || e->pep_group); }
+static bool room_group_on(const ffm_engine* e) { return rooms_on(e) && e->room_group; }
+static bool steps_group(const ffm_engine* e) {
+    if (rooms_on(e)) return e->room_group;
+    return e->group && (!e->d_envp || e->pep_group);
+}
 static bool steps_lane(const ffm_engine* e) {
-    if (rooms_on(e)) return !e->room_block;
+    if (rooms_on(e)) return !e->room_block && !e->room_group;
     return e->d_envp ? e->pep_lane && !e->pep_group : e->lane;
 }
 static bool steps_wave(const ffm_engine* e) { return e->wave && !e->d_envp; }
@@ -157,11 +165,15 @@ constexpr int kGroupGridPerCu = 8;
 static int lane_blocks_now(const ffm_engine* e) {
     return rooms_on(e) ? e->room_lane_blocks : e->d_envp ? e->pep_lane_blocks : e->lane_blocks;
 }
-// The group kernel's launch geometry in effect: the create-time one, or the per-env form's.
-static int group_blocks_now(const ffm_engine* e) { return pep_group_on(e) ? e->pep_group_blocks : e->group_blocks; }
-static int group_g_now(const ffm_engine* e) { return pep_group_on(e) ? e->pep_group_g : e->group_g; }
+// The group kernel's launch geometry in effect: the create-time one, the per-env form's or the room form's.
+static int group_blocks_now(const ffm_engine* e) {
+    return room_group_on(e) ? e->room_group_blocks : pep_group_on(e) ? e->pep_group_blocks : e->group_blocks;
+}
+static int group_g_now(const ffm_engine* e) {
+    return room_group_on(e) ? e->room_group_g : pep_group_on(e) ? e->pep_group_g : e->group_g;
+}
 static const std::vector<ffm_engine::Shard>& shards_now(const ffm_engine* e) {
-    return pep_group_on(e) ? e->pep_shards : e->shards;
+    return room_group_on(e) ? e->room_shards : pep_group_on(e) ? e->pep_shards : e->shards;
 }
 
 // The lane kernel's persistent grid for n_envs envs (a.envp set: of its per-env form).
@@ -208,13 +220,16 @@ static void free_episode_log(ffm_engine* e, bool ep_start_too) {
 
 // The group kernel's launch geometry for n_envs envs: envs per group, the one-launch grid and the
 // step shards (empty: one launch per step), from the resident blocks of the kernel form `a` names
-// (a.envp set: the per-env form).
+// (a.envp set: the per-env form; a.rooms set: the room form).
+// room: the room form's grids.  That form is the single-group form only and not persistent, so every
+// launch holds a wave per group, ceil(groups / 4) blocks: neither the residency cap nor
+// FFM_WAVE_BLOCKS applies (a wave without a group skips the step).
 struct GroupGeom {
     int g = 4, blocks = 0;
     std::vector<ffm_engine::Shard> shards;
     size_t shard_slots = 0;   // counter slots of the step shards, one range each
 };
-static GroupGeom group_geometry(const ffm::CoreStepArgs& a, int nb, long long n_envs, int cus) {
+static GroupGeom group_geometry(const ffm::CoreStepArgs& a, int nb, long long n_envs, int cus, bool room = false) {
     GroupGeom gg;
     // The loop form's resident blocks, at most 6 (6 waves per SIMD) per CU: what the shard
     // rule and the group-size picker count with (as a one-launch grid, 7 per CU stepped
@@ -230,6 +245,7 @@ static GroupGeom group_geometry(const ffm::CoreStepArgs& a, int nb, long long n_
     // resident; profiles/one_group/), the persistent loop beyond.
     auto group_grid = [&](long long n, int G) {
         const long long groups = (n + G - 1) / G;
+        if (room) return (int)std::max<long long>(1, (groups + 3) / 4);
         long long b = std::max<long long>(1, std::min<long long>((groups + 3) / 4, (long long)cus * kGroupGridPerCu));
         if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {   // diagnostic override of the grid
             const long long v = std::atoll(ov);
@@ -682,6 +698,7 @@ static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
             a.episodes = base.episodes + sh.e0;
             if (base.ep_start) a.ep_start = base.ep_start + sh.e0;   // records carry global ids through env_base
             if (base.envp) a.envp = base.envp + sh.e0;
+            if (base.room_of_env) a.room_of_env = base.room_of_env + sh.e0;
             a.counters = base.counters + 4 * sh.ctr0;
             a.no_step_count = k != 0;   // one shard per step counts the step
             he = ffm::launch_core_group(a, e->d.neighborhood, sh.blocks, k ? e->sh_stream[k - 1] : s, sh.g, e->group_one);
@@ -1293,6 +1310,9 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
         e->room_fmax = 0;
         e->room_lane_blocks = 0;
         e->room_block = false;
+        e->room_group = false;
+        e->room_group_blocks = 0;
+        e->room_shards.clear();
         e->room_maps.clear();
         e->room_sffs.clear();
         e->room_of_env.clear();
@@ -1301,9 +1321,9 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     }
     if (e->mt) return fail(FFM_E_UNSUPPORTED, "env rooms: Philox engines only");
     if (e->f64) return fail(FFM_E_UNSUPPORTED, "env rooms: float32-SFF engines only");
-    // the block kernel's room form where the engine's setting asks for it (ffm_engine_set_env_rooms_kernel,
-    // which accepted the engine); else the lane kernel's
-    const bool block_form = e->room_kernel == 1;
+    // the block kernel's room form (mode 1) or the group kernel's (mode 2) where the engine's setting asks
+    // for it (ffm_engine_set_env_rooms_kernel, which accepted the engine); else the lane kernel's
+    const bool block_form = e->room_kernel == 1, group_form = e->room_kernel == 2;
     if (!block_form && !e->lane_ok)
         return fail(FFM_E_UNSUPPORTED, "env rooms: engines of the lane kernel's shapes only (agent_capacity <= 32, W % 4 == 0, H*W <= 256)");
     if (n_rooms < 1 || n_rooms > e->d.n_envs) return fail(FFM_E_INVALID, "env rooms: n_rooms must lie in [0, n_envs]");
@@ -1327,7 +1347,10 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     }
     for (size_t i = 0; i < E; i++)
         if (room_of_env[i] < 0 || room_of_env[i] >= n_rooms) return fail(FFM_E_INVALID, "env rooms: room_of_env out of range");
-    if (!block_form && ffm::core_lane_smem_bytes(H, W, fmax, 4, true) > 64 * 1024)
+    if (group_form && std::max(ffm::core_group_smem_bytes(H, W, fmax, 4, 2, true, true),
+                               ffm::core_group_smem_bytes(H, W, fmax, 4, 4, true, true)) > 64 * 1024)
+        return fail(FFM_E_UNSUPPORTED, "env rooms: the group kernel's LDS has no room for the largest room");
+    if (!block_form && !group_form && ffm::core_lane_smem_bytes(H, W, fmax, 4, true) > 64 * 1024)
         return fail(FFM_E_UNSUPPORTED, "env rooms: the lane kernel's LDS has no room for the largest room");
     if (block_form) {
         // the block kernel at the create-time K with the largest room's F, the K records and room indices
@@ -1378,10 +1401,12 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     unsigned char* d_rooms = nullptr;
     int32_t* d_roe = nullptr;
     ffm::EnvParams* d_envp = nullptr;
+    unsigned long long* d_ctr = nullptr;   // the group form: a larger counter array, if its grids need one
     auto undo = [&](int rc) {
         (void)hipFree(d_rooms);
         (void)hipFree(d_roe);
         (void)hipFree(d_envp);
+        (void)hipFree(d_ctr);
         return rc;
     };
     // room_of_env is read in pairs through buffer resources: whole pairs, zeroed padding
@@ -1391,7 +1416,26 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     if (he == hipSuccess) he = hipMalloc((void**)&d_envp, E * sizeof(ffm::EnvParams));
     if (he != hipSuccess) return undo(fail(FFM_E_NOMEM, std::string("env rooms: ") + hipGetErrorString(he)));
     int lane_blocks = 0;
-    if (!block_form) {
+    GroupGeom rg;
+    size_t ctr_slots = e->ctr_slots;
+    if (group_form) {
+        // The group kernel's room form: envs per group and step shards from that form's occupancy, as
+        // the per-env form's (pep_group_setup); every launch's grid holds a wave per group.  The kernel
+        // adds to one counter slot per wave of its grid, so a geometry with more waves than the slots
+        // allocated at create gets a larger array, the sums carried over (below): the create-time
+        // kernels keep their arguments and resources.
+        ffm::CoreStepArgs a{};
+        a.H = H; a.W = W; a.A = e->d.agent_capacity; a.F = fmax; a.auto_reset = e->d.auto_reset;
+        a.envp = d_envp; a.rooms = d_rooms; a.room_of_env = d_roe;   // the occupancy of the room form
+        rg = group_geometry(a, e->d.neighborhood, e->d.n_envs, cus, true);
+        ctr_slots = std::max(ctr_slots, std::max((size_t)rg.blocks * 4, rg.shard_slots));
+        if (ctr_slots > e->ctr_slots) {
+            he = hipMalloc((void**)&d_ctr, ctr_slots * 32);
+            if (he != hipSuccess) return undo(fail(FFM_E_NOMEM, std::string("env rooms: counters: ") + hipGetErrorString(he)));
+        }
+        he = ensure_shard_streams(e, rg.shards.size());
+        if (he != hipSuccess) return undo(fail(FFM_E_HIP, std::string("step shard streams: ") + hipGetErrorString(he)));
+    } else if (!block_form) {
         ffm::CoreStepArgs a{};
         a.H = H; a.W = W; a.A = e->d.agent_capacity; a.F = fmax; a.auto_reset = e->d.auto_reset;
         a.envp = d_envp; a.rooms = d_rooms; a.room_of_env = d_roe;   // the occupancy of the room form
@@ -1404,8 +1448,15 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     if (he == hipSuccess) he = hipMemcpyAsync(d_roe, room_of_env, E * 4, hipMemcpyHostToDevice, s);
     if (he == hipSuccess) he = hipMemcpyAsync(d_rooms, table.data(), table.size(), hipMemcpyHostToDevice, s);
     if (he == hipSuccess) he = hipMemcpyAsync(d_envp, rec.data(), E * sizeof(ffm::EnvParams), hipMemcpyHostToDevice, s);
+    if (he == hipSuccess && d_ctr) he = hipMemsetAsync(d_ctr, 0, ctr_slots * 32, s);
+    if (he == hipSuccess && d_ctr) he = hipMemcpyAsync(d_ctr, e->d_ctr, e->ctr_slots * 32, hipMemcpyDeviceToDevice, s);
     if (he == hipSuccess) he = hipStreamSynchronize(s);
     if (he != hipSuccess) return undo(fail(FFM_E_HIP, std::string("env rooms: ") + hipGetErrorString(he)));
+    if (d_ctr) {   // the larger counter array stays for the engine's life (ffm_engine_device_buffers reports it)
+        (void)hipFree(e->d_ctr);
+        e->d_ctr = d_ctr;
+        e->ctr_slots = ctr_slots;
+    }
     (void)hipFree(e->d_rooms);
     (void)hipFree(e->d_room_of_env);
     (void)hipFree(e->d_envp);
@@ -1416,6 +1467,10 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     e->room_fmax = fmax;
     e->room_lane_blocks = lane_blocks;
     e->room_block = block_form;
+    e->room_group = group_form;
+    e->room_group_g = rg.g;
+    e->room_group_blocks = rg.blocks;
+    e->room_shards = std::move(rg.shards);
     e->room_maps.assign(maps, maps + (size_t)n_rooms * HW);
     e->room_sffs.assign(sffs, sffs + (size_t)n_rooms * HW);
     e->room_of_env.assign(room_of_env, room_of_env + E);
@@ -1425,8 +1480,12 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
 
 int ffm_engine_set_env_rooms_kernel(ffm_engine* e, int32_t mode) {
     if (!e) return fail(FFM_E_INVALID, "null engine");
-    if (mode != 0 && mode != 1) return fail(FFM_E_INVALID, "env rooms kernel: mode must be 0 (lane) or 1 (block)");
+    if (mode != 0 && mode != 1 && mode != 2)
+        return fail(FFM_E_INVALID, "env rooms kernel: mode must be 0 (lane), 1 (block) or 2 (group)");
     if (rooms_on(e)) return fail(FFM_E_INVALID, "env rooms kernel: rooms are on (turn them off first)");
+    if (mode == 2 && (!e->group || e->mt || e->f64))
+        return fail(FFM_E_UNSUPPORTED, "env rooms kernel: the engine was not created on the group kernel (12x12, "
+                                       "agent_capacity <= 32, Philox, float32 SFF)");
     if (mode == 1) {
         if (e->mt) return fail(FFM_E_UNSUPPORTED, "env rooms kernel: Philox engines only");
         if (e->f64) return fail(FFM_E_UNSUPPORTED, "env rooms kernel: float32-SFF engines only");
@@ -1518,7 +1577,9 @@ int ffm_debug_group_occupancy(ffm_engine* e, int32_t one, int32_t* blocks_per_cu
     if (!e->group) return FFM_OK;
     HIP_TRY(hipSetDevice(e->d.device));
     ffm::CoreStepArgs a = make_args(e);
-    if (!pep_group_on(e)) a.envp = nullptr;   // the form that steps the engine (the per-env one only while it does)
+    // the form that steps the engine (the per-env one, or the room form, only while it does)
+    if (!pep_group_on(e) && !room_group_on(e)) a.envp = nullptr;
+    if (!room_group_on(e)) a.rooms = nullptr;
     *blocks_per_cu = ffm::core_group_blocks_per_cu(a, e->d.neighborhood, group_g_now(e), one != 0);
     return FFM_OK;
 }
@@ -1553,7 +1614,8 @@ int ffm_debug_launch_info(ffm_engine* e, int32_t* out, int n) {
     const int32_t step_blocks = group ? group_blocks_now(e) : lane ? lane_blocks_now(e) : wave ? e->wave_blocks
                                                                                         : (int32_t)((E + e->K - 1) / e->K);
     bool one = group && e->group_one;
-    if (one && S > 1) {
+    if (room_group_on(e)) one = true;   // the room form is the single-group form on every grid
+    else if (one && S > 1) {
         for (const ffm_engine::Shard& sh : shards_now(e)) one = one && ffm::core_group_one_group(sh.n, sh.blocks, sh.g);
     } else if (one) {
         one = ffm::core_group_one_group(E, group_blocks_now(e), group_g_now(e));

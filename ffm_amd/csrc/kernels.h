@@ -83,7 +83,8 @@ struct CoreStepArgs {
     // Per-env rooms (ffm_engine_set_env_rooms): the room table (one record of room_stride bytes per
     // room, room_layout below) and the [E] room index of every env, or nullptr (off: pmap, psff and
     // the free lists above hold for every env).  While set, envp is set too, F above is the largest
-    // room's (the LDS sizes) and the launchers pick the lane, block and reset kernels' ROOM instantiations.
+    // room's (the LDS sizes) and the launchers pick the lane, group, block and reset kernels' ROOM
+// instantiations (the group kernel's is its single-group form: a wave of the grid per group).
     const unsigned char* rooms;
     const int* room_of_env;
     int room_stride;
@@ -134,7 +135,8 @@ size_t core_lane_smem_bytes(int H, int W, int F, int waves, bool room = false); 
 hipError_t launch_core_lane(const CoreStepArgs& a, int nb, int blocks, hipStream_t s);
 int core_lane_blocks_per_cu(const CoreStepArgs& a, int nb);
 int core_lane_max_pairs_per_wave();
-size_t core_group_smem_bytes(int H, int W, int F, int waves, int G = 4, bool one = false);   // one: the single-group form's
+// one: the single-group form's; room: the room form's (per-env rooms, F the largest room's)
+size_t core_group_smem_bytes(int H, int W, int F, int waves, int G = 4, bool one = false, bool room = false);
 bool core_group_supported(int H, int W);
 int core_group_max_iters();
 // The stage image of the group kernel (CoreStepArgs::stage): its size, the float4s of its
@@ -147,7 +149,8 @@ void core_group_stage_build(int H, int W, int F, const uint8_t* pmap, const floa
 int core_group_pick_envs(const CoreStepArgs& a, int nb, long long E, int cus);   // envs per group (2 or 4)
 hipError_t launch_core_group(const CoreStepArgs& a, int nb, int blocks, hipStream_t s, int G, bool one = true);
 bool core_group_one_group(long long E, int blocks, int G);   // every wave of the grid steps at most one group
-int core_group_blocks_per_cu(const CoreStepArgs& a, int nb, int G, bool one = false);   // one: of the single-group form
+// one: of the single-group form; a.rooms set: of the room form
+int core_group_blocks_per_cu(const CoreStepArgs& a, int nb, int G, bool one = false);
 size_t core_multi_smem_bytes(int H, int W, int F, int waves);
 hipError_t launch_core_multi(const CoreStepArgs& a, int nb, int nsteps, int blocks, hipStream_t s);
 int core_multi_blocks_per_cu(const CoreStepArgs& a, int nb);

@@ -453,7 +453,7 @@ class Engine:
         return [{k: getattr(q, k) for k in ENV_PARAM_KEYS} for q in arr], soe
 
     # -- per-env rooms -----------------------------------------------------------
-    _ENV_ROOMS_KERNELS = {"lane": 0, "block": 1}
+    _ENV_ROOMS_KERNELS = {"lane": 0, "block": 1, "group": 2}
 
     def set_env_rooms(self, rooms, room_of_env=None, stream=None, kernel=None):
         """A geometry sweep in one engine (ffm_engine_set_env_rooms): env e runs in
@@ -468,14 +468,19 @@ class Engine:
         and 12x12 group engines only: MT, float64-SFF, wave and block engines raise
         NotImplementedError.
 
-        `kernel`: "lane", "block" or None (the engine's setting, "lane" at create, stays); sticky
-        (ffm_engine_set_env_rooms_kernel).  "block" is the block kernel's room form, for "wave"
-        and "block" engines (rooms beyond the lane kernel's shapes): while on the engine steps with
-        the block kernel.  On lane, group, MT, float64-SFF and "block_scratch" engines it raises
-        NotImplementedError; changing the kernel while rooms are on raises ValueError (turn them
-        off first).  A failed call changes nothing, the setting included."""
+        `kernel`: "lane", "block", "group" or None (the engine's setting, "lane" at create, stays);
+        sticky (ffm_engine_set_env_rooms_kernel).  "block" is the block kernel's room form, for
+        "wave" and "block" engines (rooms beyond the lane kernel's shapes): while on the engine
+        steps with the block kernel.  On lane, group, MT, float64-SFF and "block_scratch" engines
+        it raises NotImplementedError.  "group" is the group kernel's room form, the opt-in fast
+        path for sweeps on 12x12 "group" engines: while on the engine stays on the group kernel
+        (its single-group form, a wave of every launch's grid per group of envs; step shards as on
+        a homogeneous engine; FFM_WAVE_BLOCKS does not shrink that grid), same bits as the lane
+        form.  On every other engine (lane, wave, block, "block_scratch", MT, float64 SFF) it
+        raises NotImplementedError.  Changing the kernel while rooms are on raises ValueError
+        (turn them off first).  A failed call changes nothing, the setting included."""
         if kernel is not None and kernel not in self._ENV_ROOMS_KERNELS:
-            raise ValueError(f"kernel must be None, 'lane' or 'block', got {kernel!r}")
+            raise ValueError(f"kernel must be None, 'lane', 'block' or 'group', got {kernel!r}")
         rooms = list(rooms) if rooms is not None else []
         if not rooms:
             _check(self._L.ffm_engine_set_env_rooms(self._h, None, None, 0, None, _stream_handle(stream)))
@@ -745,7 +750,8 @@ class Engine:
         over all envs) with the blocks of one shard's grid, and whether those launches take the
         group kernel's single-group form ("group_one"; False: its loop form, or another kernel).
         "env_rooms": the room count of set_env_rooms(), 0 while off (on: the lane kernel, or with
-        kernel="block" the block kernel; one shard)."""
+        kernel="block" the block kernel, one shard each; with kernel="group" the group kernel,
+        "group_one" True, with that form's own blocks and shards)."""
         v = np.zeros(10, np.int32)
         _check(self._L.ffm_debug_launch_info(self._h, _ptr(v), len(v)))
         rooms = C.c_int32()

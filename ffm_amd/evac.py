@@ -36,7 +36,9 @@ the same bits either way; the default (SWEEP_KERNEL_DEFAULT) is the one that mea
 
 Rooms beyond the lane kernel's shapes (an engine whose kernel is ``wave`` or ``block``, such as the
 reference's 50x50 room) sweep with the block kernel's room form, which the driver picks by itself
-(``room_sweep_kernel``).  ``--sff geodesic`` gives rooms made by ``--room`` the obstacle-aware static
+(``room_sweep_kernel``).  ``--room-kernel {lane,group,block}`` names the room form instead
+(``Engine.set_env_rooms``'s ``kernel``): ``group`` is the group kernel's own room form for 12x12
+engines, opt-in, same outputs as the lane form.  ``--sff geodesic`` gives rooms made by ``--room`` the obstacle-aware static
 floor field (``data.geodesic_sff``) instead of the L1 distance; on rooms without obstacles the two
 are the same bits.
 
@@ -226,6 +228,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="the kernel that steps a sweep in an engine born on the group kernel (12x12): the lane "
                          f"kernel's per-env form or the group kernel's own (default: {SWEEP_KERNEL_DEFAULT}; "
                          "same outputs either way)")
+    ap.add_argument("--room-kernel", choices=("lane", "group", "block"), default=None,
+                    help="the kernel that steps a room sweep (Engine.set_env_rooms' kernel): lane, the group kernel's "
+                         "own room form (12x12 engines, opt-in) or block (default: the driver's pick, "
+                         "room_sweep_kernel; same outputs whichever runs)")
     ap.add_argument("--out", required=True, metavar="DIR")
     return ap
 
@@ -285,7 +291,8 @@ def main(argv=None):
     try:   # before the reset: its placement takes each env's own room and N
         if rooms:
             eng.set_env_rooms(rooms, np.array([sets[p]["room"] for p in soe], np.int32),
-                              kernel=room_sweep_kernel(eng.launch_info()))
+                              kernel=a.room_kernel if a.room_kernel is not None
+                              else room_sweep_kernel(eng.launch_info()))
         if sets and (sweeps or not rooms):
             # the room axis is the slowest: combination c has the parameters of combination c % Pp
             n_par = len(sets) // max(1, len(rooms) if rooms else 1)

@@ -309,7 +309,8 @@ int ffm_engine_set_env_params_kernel(ffm_engine* eng, int32_t mode);
  *
  * Scope: 12x12 group engines and lane engines.  Wave and block engines take the block kernel's
  * room form, which is opt-in: ffm_engine_set_env_rooms_kernel(eng, 1) below.  Without it this
- * call refuses them as above.
+ * call refuses them as above.  12x12 group engines also have the group kernel's own room form,
+ * opt-in as well: ffm_engine_set_env_rooms_kernel(eng, 2).
  *
  * May be called between steps; stream-ordered on `stream`, which it synchronises: the tables are
  * consumed before it returns.  The room holds from the next launch.  An env whose room changes
@@ -326,8 +327,8 @@ int ffm_engine_set_env_params_kernel(ffm_engine* eng, int32_t mode);
  * Turning either feature off rebuilds what the other needs.
  *
  * Kernel: while rooms are on the engine steps with the lane kernel's room form (or the block
- * kernel's: ffm_engine_set_env_rooms_kernel), one launch per
- * step: step shards and fused steps are off (ffm_engine_set_fused_steps(k > 1) is accepted and
+ * kernel's or the group kernel's: ffm_engine_set_env_rooms_kernel), one launch per
+ * step: step shards (but for the group kernel's form, below) and fused steps are off (ffm_engine_set_fused_steps(k > 1) is accepted and
  * ignored meanwhile, as under trajectory capture), and a sticky
  * ffm_engine_set_env_params_kernel(eng, 1) is remembered and resumes when rooms are turned off.
  * Trajectory capture, the episode log and statistics, ffm_engine_reset_envs,
@@ -342,8 +343,10 @@ int ffm_engine_get_env_rooms(ffm_engine* eng, uint8_t* maps, float* sffs, int32_
 /* The kernel that steps the engine while rooms are on: mode 0 = lane (the create-time default:
  * ffm_engine_set_env_rooms behaves as described above), mode 1 = block -- the block kernel's room
  * form, for rooms beyond the lane kernel's shapes (the reference's 50x50 room, 64x64 with hundreds
- * of agents).  Sticky: read by the next ffm_engine_set_env_rooms.  FFM_E_INVALID: another value,
- * or rooms are on (turn them off first).
+ * of agents), mode 2 = group -- the group kernel's room form, the opt-in fast path for geometry
+ * sweeps in 12x12 engines.  Sticky: read by the next ffm_engine_set_env_rooms, and independent of
+ * ffm_engine_set_env_params_kernel.  FFM_E_INVALID: another value, or rooms are on (turn them off
+ * first).
  *
  * Mode 1 is accepted on Philox, float32-SFF engines whose create-time kernel is the wave or the
  * block kernel.  FFM_E_UNSUPPORTED, nothing changed: lane and group engines (they have the lane
@@ -359,7 +362,28 @@ int ffm_engine_get_env_rooms(ffm_engine* eng, uint8_t* maps, float* sffs, int32_
  * nothing changed if one fails.  While on, the engine steps with the block kernel (a wave engine
  * moves to it, as under ffm_engine_set_env_params), fused steps do not apply, and everything
  * said above about composition, resets, the log, capture and update_dff holds.  n_rooms = 0
- * restores the create-time kernel and grid. */
+ * restores the create-time kernel and grid.
+ *
+ * Mode 2 is accepted on Philox, float32-SFF engines created on the group kernel (12x12,
+ * agent_capacity <= 32).  FFM_E_UNSUPPORTED, nothing changed: lane, wave, block and block_scratch
+ * engines, MT and float64-SFF engines.
+ *
+ * With mode 2 set, ffm_engine_set_env_rooms validates as above, builds the same room table and
+ * per-env records, and takes the launch geometry of the group kernel's room form: envs per group
+ * (2 or 4; FFM_GROUP_ENVS) and step shards (FFM_STEP_SHARDS) from that form's occupancy, as
+ * ffm_engine_set_env_params_kernel(eng, 1) does for the per-env form.  The form is the kernel's
+ * single-group form only: every launch's grid holds one wave per group, ceil(groups / 4) blocks,
+ * whatever is resident, and the diagnostic FFM_WAVE_BLOCKS does not shrink it.  Where those grids
+ * have more waves than the counter array has slots, the array is replaced by a larger one with the
+ * sums carried over (ffm_engine_device_buffers then reports the new pointer and slot count; it
+ * stays for the engine's life).  FFM_E_UNSUPPORTED with nothing changed only if the form's LDS at
+ * the largest room's free-cell count exceeds 64 KB.  While on, the engine stays on the group kernel
+ * with the bits of the lane form: step shards apply as on a homogeneous group engine (one shard
+ * under trajectory capture), fused steps do not, ffm_engine_reset and ffm_engine_reset_envs place
+ * from each env's room as in the other forms, and everything said above about composition with
+ * ffm_engine_set_env_params (in either order; a remembered ffm_engine_set_env_params_kernel
+ * choice stays as it was), the log, capture and update_dff holds.  n_rooms = 0 restores the
+ * create-time kernel, grid and shards. */
 int ffm_engine_set_env_rooms_kernel(ffm_engine* eng, int32_t mode);
 
 /* counters[4] = {agent_steps, exits, resets, steps} accumulated since create. */
