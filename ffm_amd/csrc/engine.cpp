@@ -44,18 +44,36 @@ int fail(int code, const std::string& msg) { return ffm::set_error(code, msg); }
 
 }  // namespace
 
+// How a step is launched: the step kernel, its one-launch grid and, for the group kernel, the envs
+// per group, its form, the step shards and the stage image.  The engine keeps one plan per form
+// (create, per-env parameters on the lane / block kernel, per-env parameters on the group kernel,
+// per-env rooms); plan() below picks the one in effect.
+struct StepPlan {
+    enum Kernel { kGroup = 0, kLane = 1, kWave = 2, kBlock = 3 };   // ffm_debug_launch_info's out[0]
+    Kernel kernel = kBlock;
+    int blocks = 0;              // the one-launch grid
+    int g = 0;                   // group kernel: envs per group (core_group_pick_envs)
+    bool one = false;            // ... the single-group form where a grid allows it (FFM_GROUP_ONE; the room
+                                 // form has no other)
+    // Step shards (group kernel, ffm_engine_step with n_steps > 1): disjoint env ranges, each
+    // stepped by launches of its own on a stream of its own, so the fill and drain of one
+    // shard's launch overlap the body of the others'.  Shard 0 runs on the caller's stream.
+    struct Shard {
+        long long e0 = 0, n = 0;   // first env, env count (e0 a multiple of 8)
+        int blocks = 0, g = 4;     // its grid and envs per group
+        size_t ctr0 = 0;           // its first counter slot
+    };
+    std::vector<Shard> shards;   // size() <= 1: off
+    // The stage image (kernels.h): the engine's, or for the per-env form d_stage_raw.  Null on
+    // engines not created on the group kernel; the other kernels do not read it.
+    const unsigned char* stage = nullptr;
+};
+
 struct ffm_engine {
     ffm_engine_desc d{};
     int HW = 0, F = 0, K = 1, block = 256;
+    int cus = 0;                 // the device's CUs (the persistent grids)
     bool f64 = false, mt = false;
-    bool lane = false;      // lane kernel (Philox, A <= 32, W % 4 == 0, H*W <= 256): core_lane.hip
-    bool wave = false;      // wave-per-env kernel (A <= 64) vs block-per-env kernel
-    int wave_blocks = 0;    // persistent grid of the wave kernel
-    int lane_blocks = 0;    // persistent grid of the lane kernel
-    bool group = false;     // group kernel (lane conditions at 12x12): core_group.hip
-    int group_blocks = 0;   // persistent grid of the group kernel
-    int group_g = 4;        // envs per group (core_group_pick_envs)
-    bool group_one = true;  // the single-group form where a grid allows it (FFM_GROUP_ONE)
     bool multi = false;     // multi-step kernel available (lane conditions): core_multi.hip
     int multi_blocks = 0;   // its persistent grid
     int fused = 1;          // steps per launch (ffm_engine_set_fused_steps)
@@ -93,36 +111,23 @@ struct ffm_engine {
     long long eplog_cap = 0;
     unsigned long long* d_ephist = nullptr;   // [ephist_bins] histogram, then the summary's slots
     int ephist_bins = 0;
-    // Step shards (group kernel, ffm_engine_step with n_steps > 1): disjoint env ranges, each
-    // stepped by launches of its own on a stream of its own, so the fill and drain of one
-    // shard's launch overlap the body of the others'.  Shard 0 runs on the caller's stream.
-    struct Shard {
-        long long e0 = 0, n = 0;   // first env, env count (e0 a multiple of 8)
-        int blocks = 0, g = 4;     // its grid and envs per group
-        size_t ctr0 = 0;           // its first counter slot
-    };
-    std::vector<Shard> shards;   // size() <= 1: off
-    hipStream_t sh_stream[3] = {nullptr, nullptr, nullptr};   // shards 1..3
+    // The step plans, one per form (plan() picks), and when each is filled:
+    StepPlan create_plan;      // ffm_engine_create: the lane, group, wave or block kernel
+    StepPlan pep_plan;         // each ffm_engine_set_env_params: the lane kernel's per-env form on lane and group
+                               // engines, the block kernel's on the others (the wave kernel has none)
+    StepPlan pep_group_plan;   // the group kernel's own per-env form, when the feature moves to it (pep_group_setup)
+    StepPlan room_plan;        // each ffm_engine_set_env_rooms: the lane, block or group form by room_kernel
+    hipStream_t sh_stream[3] = {nullptr, nullptr, nullptr};   // step shards 1..3
     hipEvent_t sh_fork = nullptr;
     hipEvent_t sh_end[3] = {nullptr, nullptr, nullptr};
-    // Per-env parameters (ffm_engine_set_env_params): null / empty while off.  While on, an
-    // engine of the group kernel steps with the lane kernel's per-env form, or, if asked
-    // (ffm_engine_set_env_params_kernel), with the group kernel's own; one of the wave kernel
-    // steps with the block kernel (it has no per-env form); the others keep their kernel.
+    // Per-env parameters (ffm_engine_set_env_params): null / empty while off.
     ffm::EnvParams* d_envp = nullptr;          // [n_envs] records (kernels.h)
     std::vector<ffm_env_params> pep_sets;      // the caller's tables, for ffm_engine_get_env_params
     std::vector<int32_t> pep_set_of_env;
-    bool pep_lane = false;                     // step with the lane kernel
-    int pep_lane_blocks = 0;                   // its persistent grid
     int pep_kernel = 0;                        // ffm_engine_set_env_params_kernel's mode (sticky)
-    bool pep_group = false;                    // step with the group kernel's per-env form (mode 1, feature on)
-    int pep_group_blocks = 0, pep_group_g = 4; // its grid and envs per group, from that form's occupancy
-    std::vector<Shard> pep_shards;             // ... and its step shards (size() <= 1: off)
-    unsigned char* d_stage_raw = nullptr;      // its stage image: the SFF term with multiplier 1 (the raw SFF);
-                                               // built when the feature first moves to the group kernel
-    // Per-env rooms (ffm_engine_set_env_rooms): null / empty while off.  While on the engine steps
-    // with the lane kernel's room form, or (room_block) the block kernel's, or (room_group) the group
-    // kernel's, and d_envp holds a
+    unsigned char* d_stage_raw = nullptr;      // the per-env group form's stage image: the SFF term with multiplier 1
+                                               // (the raw SFF); built when the feature first moves to the group kernel
+    // Per-env rooms (ffm_engine_set_env_rooms): null / empty while off.  While on, d_envp holds a
     // record per env: the caller's sets', or (pep_sets empty) the create-time values, each with
     // its room's placement threshold.
     bool lane_ok = false;                      // the lane kernel's conditions hold (create)
@@ -130,66 +135,117 @@ struct ffm_engine {
     int32_t* d_room_of_env = nullptr;          // [n_envs]
     size_t room_stride = 0;
     int room_fmax = 0;                         // the largest room's free-cell count
-    int room_lane_blocks = 0;                  // the lane room form's persistent grid
     int room_kernel = 0;                       // ffm_engine_set_env_rooms_kernel's mode (sticky)
-    bool room_block = false;                   // rooms are on in the block kernel's form (mode 1)
-    bool room_group = false;                   // rooms are on in the group kernel's form (mode 2)
-    int room_group_blocks = 0, room_group_g = 4;   // its one-launch grid (a wave per group) and envs per group
-    std::vector<Shard> room_shards;            // ... and its step shards (size() <= 1: off)
     std::vector<uint8_t> room_maps;            // the caller's tables, for ffm_engine_get_env_rooms
     std::vector<float> room_sffs;
     std::vector<int32_t> room_of_env;
     std::vector<int> room_f;                   // free cells of every room
 };
 
+// The two features.  Invariants the setters keep:
+//   d_envp != nullptr  <=>  rooms_on || pep_on   (rooms keep a record per env even without sets);
+//   pep_sets non-empty =>   d_envp != nullptr;
+//   pep_on && pep_kernel == 1  =>  pep_group_plan is filled (and d_stage_raw built);
+//   pep_on             =>   pep_plan is filled;   rooms_on  =>  room_plan is filled.
 static bool rooms_on(const ffm_engine* e) { return e->d_rooms != nullptr; }
 // Per-env parameters as the caller set them (the records of an engine with rooms only are the engine's own).
 static bool pep_on(const ffm_engine* e) { return e->d_envp && !e->pep_sets.empty(); }
 
-// The kernel that steps the engine under its current settings (per-env parameters move group and
-// wave engines): at most one of these holds, none means the block kernel.
-static bool pep_group_on(const ffm_engine* e) { return !rooms_on(e) && e->d_envp && e->pep_group; }
-static bool room_group_on(const ffm_engine* e) { return rooms_on(e) && e->room_group; }
-static bool steps_group(const ffm_engine* e) {
-    if (rooms_on(e)) return e->room_group;
-    return e->group && (!e->d_envp || e->pep_group);
+// The plan that steps the engine under its current settings.  Rooms go first: turning them off
+// returns to the per-env plan computed earlier (or the create plan), never to a fresh one.
+static const StepPlan& plan(const ffm_engine* e) {
+    if (rooms_on(e)) return e->room_plan;
+    if (pep_on(e)) return e->pep_kernel == 1 ? e->pep_group_plan : e->pep_plan;
+    return e->create_plan;
 }
-static bool steps_lane(const ffm_engine* e) {
-    if (rooms_on(e)) return !e->room_block && !e->room_group;
-    return e->d_envp ? e->pep_lane && !e->pep_group : e->lane;
+static bool created_on(const ffm_engine* e, StepPlan::Kernel k) { return e->create_plan.kernel == k; }
+
+// Counter slots the plan's launches add to: one per wave of a grid (per block of the block
+// kernel's), the step shards a range each.
+static size_t plan_slots(const StepPlan& p) {
+    size_t n = (size_t)p.blocks * (p.kernel == StepPlan::kBlock ? 1 : 4);
+    if (!p.shards.empty()) n = std::max(n, p.shards.back().ctr0 + (size_t)p.shards.back().blocks * 4);
+    return n;
 }
-static bool steps_wave(const ffm_engine* e) { return e->wave && !e->d_envp; }
-// Blocks per CU of the group kernel's largest grid (engine create, group_grid).
+
+// Blocks per CU of the group kernel's largest grid (engine create, group_plan).
 constexpr int kGroupGridPerCu = 8;
 
-static int lane_blocks_now(const ffm_engine* e) {
-    return rooms_on(e) ? e->room_lane_blocks : e->d_envp ? e->pep_lane_blocks : e->lane_blocks;
-}
-// The group kernel's launch geometry in effect: the create-time one, the per-env form's or the room form's.
-static int group_blocks_now(const ffm_engine* e) {
-    return room_group_on(e) ? e->room_group_blocks : pep_group_on(e) ? e->pep_group_blocks : e->group_blocks;
-}
-static int group_g_now(const ffm_engine* e) {
-    return room_group_on(e) ? e->room_group_g : pep_group_on(e) ? e->pep_group_g : e->group_g;
-}
-static const std::vector<ffm_engine::Shard>& shards_now(const ffm_engine* e) {
-    return room_group_on(e) ? e->room_shards : pep_group_on(e) ? e->pep_shards : e->shards;
+// A persistent grid for `units` (envs, env pairs or groups, one per wave at a time, 4 waves per
+// block): min(ceil(units / 4), cus * per_cu) blocks.  FFM_WAVE_BLOCKS=<n> overrides the residency
+// cap (diagnostic; read at create and when a form's geometry is taken).  per_wave > 0: the units a
+// wave can step in one launch (its deferred-reset mask); beyond that the grid grows past one
+// resident wave of blocks.
+static int persistent_grid(long long units, int cus, int per_cu, long long per_wave = 0) {
+    const long long full = (units + 3) / 4;
+    long long b = std::max<long long>(1, std::min<long long>(full, (long long)cus * std::max(1, per_cu)));
+    if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {
+        const long long v = std::atoll(ov);
+        if (v > 0) b = std::min<long long>(v, full);
+    }
+    if (per_wave > 0) b = std::max<long long>(b, (units + 4 * per_wave - 1) / (4 * per_wave));
+    return (int)b;
 }
 
-// The lane kernel's persistent grid for n_envs envs (a.envp set: of its per-env form).
-static int lane_grid(const ffm::CoreStepArgs& a, int nb, long long n_envs, int cus) {
-    const int per_cu = std::max(1, ffm::core_lane_blocks_per_cu(a, nb));
-    const long long groups = (n_envs + 1) / 2;
-    long long b = std::max<long long>(1, std::min<long long>((groups + 3) / 4, (long long)cus * per_cu));
-    if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {   // diagnostic override of the grid
-        const long long v = std::atoll(ov);
-        if (v > 0) b = std::min<long long>(v, (groups + 3) / 4);
-    }
-    // every wave steps at most core_lane_max_pairs_per_wave() pairs (its deferred
-    // reset mask); beyond that the grid grows past one resident wave of blocks
-    const long long per_wave = ffm::core_lane_max_pairs_per_wave();
-    return (int)std::max<long long>(b, (groups + 4 * per_wave - 1) / (4 * per_wave));
+// The arguments the kernels' occupancy queries read, for the form that the tables name (envp set:
+// the per-env form; rooms and room_of_env set as well: the room form) at F free cells (the LDS sizes).
+static ffm::CoreStepArgs form_args(const ffm_engine* e, int F, const ffm::EnvParams* envp = nullptr,
+                                   const unsigned char* rooms = nullptr, const int32_t* room_of_env = nullptr) {
+    ffm::CoreStepArgs a{};
+    a.H = e->d.H; a.W = e->d.W; a.A = e->d.agent_capacity; a.F = F;
+    a.auto_reset = e->d.auto_reset && !e->mt;
+    a.envp = envp; a.rooms = rooms; a.room_of_env = room_of_env;
+    return a;
 }
+
+// The lane kernel's persistent grid, of the form `a` names.
+static int lane_grid(const ffm_engine* e, const ffm::CoreStepArgs& a) {
+    return persistent_grid((e->d.n_envs + 1) / 2, e->cus, ffm::core_lane_blocks_per_cu(a, e->d.neighborhood),
+                           ffm::core_lane_max_pairs_per_wave());
+}
+
+// A plan of a kernel without group state: the grid only.
+static StepPlan simple_plan(const ffm_engine* e, StepPlan::Kernel kernel, int blocks) {
+    StepPlan p;
+    p.kernel = kernel;
+    p.blocks = blocks;
+    p.stage = e->d_stage;
+    return p;
+}
+static int block_grid(const ffm_engine* e) { return (int)((e->d.n_envs + e->K - 1) / e->K); }
+
+// The placement's candidate count M and key threshold for N agents on F free cells (wave_reset.h):
+// about M = N + max(8, (N + 1) / 2) of the F keys fall below thr = floor(M * 2^32 / F), 48 for 32
+// agents.  FFM_RESET_CANDIDATES=<M> overrides M (A/B switch, read at create and when records are
+// built; 0: rank every key).  The division is done here, once: in the kernel it would be a loop
+// invariant that every wave sets up.
+static uint32_t placement_threshold(int N, int F, int* m_out = nullptr) {
+    int M = std::min(F, N + std::max(8, (N + 1) / 2));
+    if (const char* ov = std::getenv("FFM_RESET_CANDIDATES")) M = std::max(0, std::min(F, std::atoi(ov)));
+    if (m_out) *m_out = M;
+    return M == 0 ? 0u : M == F ? 0xFFFFFFFFu : (uint32_t)(((uint64_t)M << 32) / (uint64_t)F);
+}
+
+// The wave reset's LDS for F free cells and n agents (launch_core_reset's carve, core_step.hip).
+static size_t wave_reset_lds(int F, int n) {
+    auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    return al16(8 * (size_t)std::max(1, F)) + al16(2 * (size_t)std::max(1, n)) + al16(2 * (size_t)std::max(1, F));
+}
+
+// The free cells of a row-major H x W map as padded indices (x + 1)(W + 2) + y + 1 and, if asked
+// for, as row-major ones.  False: a free cell on the border.  The reference indexes neighbours
+// without bounds checks (model/ffm_core.py:45,52): agents must never stand on the outer ring.
+static bool scan_free(const uint8_t* map, int H, int W, std::vector<uint16_t>* padded, std::vector<uint16_t>* rowmajor = nullptr) {
+    for (int i = 0; i < H * W; i++) {
+        const int x = i / W, y = i % W;
+        if (map[i] != 0) continue;
+        if (x == 0 || y == 0 || x == H - 1 || y == W - 1) return false;
+        padded->push_back((uint16_t)((x + 1) * (W + 2) + y + 1));
+        if (rowmajor) rowmajor->push_back((uint16_t)i);
+    }
+    return true;
+}
+static const char* const kBorderError = "free cell on the map border (walls must enclose the room)";
 
 // Upper bound of FFM_STEP_SHARDS: the caller's stream + 3 of the engine's (a process has 4
 // hardware queues by default; more streams than queues only serialise).
@@ -218,48 +274,35 @@ static void free_episode_log(ffm_engine* e, bool ep_start_too) {
     }
 }
 
-// The group kernel's launch geometry for n_envs envs: envs per group, the one-launch grid and the
-// step shards (empty: one launch per step), from the resident blocks of the kernel form `a` names
-// (a.envp set: the per-env form; a.rooms set: the room form).
-// room: the room form's grids.  That form is the single-group form only and not persistent, so every
-// launch holds a wave per group, ceil(groups / 4) blocks: neither the residency cap nor
-// FFM_WAVE_BLOCKS applies (a wave without a group skips the step).
-struct GroupGeom {
-    int g = 4, blocks = 0;
-    std::vector<ffm_engine::Shard> shards;
-    size_t shard_slots = 0;   // counter slots of the step shards, one range each
-};
-static GroupGeom group_geometry(const ffm::CoreStepArgs& a, int nb, long long n_envs, int cus, bool room = false) {
-    GroupGeom gg;
-    // The loop form's resident blocks, at most 6 (6 waves per SIMD) per CU: what the shard
-    // rule and the group-size picker count with (as a one-launch grid, 7 per CU stepped
-    // slower and so did fewer than 6: profiles/r06/c2/ab_grid_balance*.log,
-    // ab_occupancy7.log).
-    auto resident_cap = [&](int G) {
-        const int per_cu = std::max(1, ffm::core_group_blocks_per_cu(a, nb, G));
-        return (long long)cus * std::min(per_cu, 6);
-    };
+// A plan of the group kernel: envs per group, the one-launch grid and the step shards (empty: one
+// launch per step), from the resident blocks of the kernel form `a` names (a.envp set: the per-env
+// form; a.rooms set: the room form), with the stage image and the FFM_GROUP_ONE setting it launches with.
+// The room form is the single-group form only and not persistent, so every launch holds a wave
+// per group, ceil(groups / 4) blocks: neither the residency cap nor FFM_WAVE_BLOCKS applies (a
+// wave without a group skips the step).
+static StepPlan group_plan(const ffm_engine* e, const ffm::CoreStepArgs& a, const unsigned char* stage, bool one) {
+    const int nb = e->d.neighborhood, cus = e->cus;
+    const long long n_envs = e->d.n_envs;
+    const bool room = a.rooms != nullptr;
+    StepPlan p;
+    p.kernel = StepPlan::kGroup;
+    p.stage = stage;
+    p.one = one || room;
     // The grid of a launch of n envs: a wave per group up to kGroupGridPerCu blocks per CU
     // (2,048 on MI355X: each of the headline's two shards of 8,192 groups then takes the
     // single-group form, whose 56 VGPRs and 22.4 KB of LDS keep 7 blocks per CU
-    // resident; profiles/one_group/), the persistent loop beyond.
+    // resident; profiles/one_group/), the persistent loop beyond; every wave steps at most
+    // core_group_max_iters() groups (its deferred-reset mask).
     auto group_grid = [&](long long n, int G) {
         const long long groups = (n + G - 1) / G;
         if (room) return (int)std::max<long long>(1, (groups + 3) / 4);
-        long long b = std::max<long long>(1, std::min<long long>((groups + 3) / 4, (long long)cus * kGroupGridPerCu));
-        if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {   // diagnostic override of the grid
-            const long long v = std::atoll(ov);
-            if (v > 0) b = std::min<long long>(v, (groups + 3) / 4);
-        }
-        // every wave steps at most core_group_max_iters() groups (its deferred-reset mask)
-        const long long per_wave = ffm::core_group_max_iters();
-        return (int)std::max<long long>(b, (groups + 4 * per_wave - 1) / (4 * per_wave));
+        return persistent_grid(groups, cus, kGroupGridPerCu, ffm::core_group_max_iters());
     };
-    gg.g = ffm::core_group_pick_envs(a, nb, n_envs, cus);
-    gg.blocks = group_grid(n_envs, gg.g);
+    p.g = ffm::core_group_pick_envs(a, nb, n_envs, cus);
+    p.blocks = group_grid(n_envs, p.g);
 
     // Step shards.  FFM_STEP_SHARDS=1..4 forces the count (A/B switch, read at create and when
-    // the per-env form's geometry is taken);
+    // a form's geometry is taken);
     // unset, kDefaultStepShards shards wherever the one-launch grid has its waves step two
     // or more groups (on MI355X from 24,577 envs on; two shards measured faster from
     // 8,192 envs on, but below that size the engine keeps the single launch its callers
@@ -267,9 +310,13 @@ static GroupGeom group_geometry(const ffm::CoreStepArgs& a, int nb, long long n_
     // count would get alone: the shards alternate on the GPU, and the slots a draining
     // launch frees take the next shard's blocks (1 / S of the resident blocks per shard
     // measured slower: profiles/step_shards/).
+    // The rule counts with the loop form's resident blocks, at most 6 (6 waves per SIMD) per CU,
+    // as the group-size picker does (as a one-launch grid, 7 per CU stepped slower and so did
+    // fewer than 6: profiles/r06/c2/ab_grid_balance*.log, ab_occupancy7.log).
     int S = kDefaultStepShards;
-    const long long groups = (n_envs + gg.g - 1) / gg.g;
-    if (groups <= resident_cap(gg.g) * 4) S = 1;
+    const long long groups = (n_envs + p.g - 1) / p.g;
+    const int per_cu = std::max(1, ffm::core_group_blocks_per_cu(a, nb, p.g));
+    if (groups <= (long long)cus * std::min(per_cu, 6) * 4) S = 1;
     if (const char* ov = std::getenv("FFM_STEP_SHARDS")) {
         const int v = std::atoi(ov);
         if (v >= 1 && v <= kMaxStepShards) S = v;
@@ -281,19 +328,18 @@ static GroupGeom group_geometry(const ffm::CoreStepArgs& a, int nb, long long n_
         const long long per = ((n_envs + S - 1) / S + 7) & ~7ll;
         size_t ctr0 = 0;
         for (long long e0 = 0; e0 < n_envs; e0 += per) {
-            ffm_engine::Shard sh;
+            StepPlan::Shard sh;
             sh.e0 = e0;
             sh.n = std::min<long long>(per, n_envs - e0);
             sh.g = ffm::core_group_pick_envs(a, nb, sh.n, cus);
             sh.blocks = group_grid(sh.n, sh.g);
             sh.ctr0 = ctr0;           // a slot range per shard: never contended on the device
             ctr0 += (size_t)sh.blocks * 4;
-            gg.shards.push_back(sh);
+            p.shards.push_back(sh);
         }
-        gg.shard_slots = ctr0;
-        if (gg.shards.size() <= 1) gg.shards.clear();
+        if (p.shards.size() <= 1) p.shards.clear();
     }
-    return gg;
+    return p;
 }
 
 // The shards' streams (shard 0 runs on the caller's) and the fork / join events, for n shards;
@@ -375,17 +421,8 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
     if (d.n_agents < 0 || d.n_agents > d.agent_capacity) return fail(FFM_E_INVALID, "n_agents > agent_capacity");
     if (d.rng_mode != FFM_RNG_PHILOX && d.rng_mode != FFM_RNG_MT) return fail(FFM_E_INVALID, "rng_mode");
     const int H = d.H, W = d.W, HW = H * W;
-    // The reference indexes neighbours without bounds checks (model/ffm_core.py:45,52):
-    // agents must never stand on the outer ring, so no border cell may be free.
-    std::vector<uint16_t> fl;
-    for (int i = 0; i < HW; i++) {
-        const int x = i / W, y = i % W;
-        const bool border = x == 0 || y == 0 || x == H - 1 || y == W - 1;
-        if (d.map[i] == 0) {
-            if (border) return fail(FFM_E_INVALID, "free cell on the map border (walls must enclose the room)");
-            fl.push_back((uint16_t)i);
-        }
-    }
+    std::vector<uint16_t> fl, fp;   // the free list, row-major and as padded indices
+    if (!scan_free(d.map, H, W, &fp, &fl)) return fail(FFM_E_INVALID, kBorderError);
     if (d.n_agents > (int)fl.size())
         return fail(FFM_E_INVALID, "Cannot take a larger sample than population when 'replace=False'");
 
@@ -395,17 +432,7 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
     e->d.sff = nullptr;
     e->HW = HW;
     e->F = (int)fl.size();
-    // Placement candidates (wave_reset.h): about M = N + max(8, (N + 1) / 2) of the F keys fall
-    // below thr = floor(M * 2^32 / F), 48 for 32 agents.  FFM_RESET_CANDIDATES=<M> overrides M
-    // (A/B switch, read at create; 0: rank every key).  The division is done here, once: in the
-    // kernel it would be a loop invariant that every wave sets up.
-    {
-        const int N = d.n_agents, F = e->F;
-        int M = std::min(F, N + std::max(8, (N + 1) / 2));
-        if (const char* ov = std::getenv("FFM_RESET_CANDIDATES")) M = std::max(0, std::min(F, std::atoi(ov)));
-        e->reset_m = M;
-        e->reset_thr = M == 0 ? 0u : M == F ? 0xFFFFFFFFu : (uint32_t)(((uint64_t)M << 32) / (uint64_t)F);
-    }
+    e->reset_thr = placement_threshold(d.n_agents, e->F, &e->reset_m);
     e->f64 = d.sff_dtype == FFM_SFF_F64;
     e->mt = d.rng_mode == FFM_RNG_MT;
     // NumPy weak-scalar promotion (NEP 50): python numbers become float32 next
@@ -435,13 +462,13 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
     const bool lane_ok = !e->mt && !e->f64 && A <= 32 && W % 4 == 0 && HW <= 256 &&
                          ((long long)d.n_envs + 7) * HW * 4 < (1ll << 31);   // 32-bit buffer offsets (padded envs)
     e->lane_ok = lane_ok;
-    e->group = (d.envs_per_block == 0 || d.envs_per_block == -3) && lane_ok && ffm::core_group_supported(H, W) &&
-               ffm::core_group_smem_bytes(H, W, e->F, 4) <= 64 * 1024;
+    const bool group = (d.envs_per_block == 0 || d.envs_per_block == -3) && lane_ok && ffm::core_group_supported(H, W) &&
+                       ffm::core_group_smem_bytes(H, W, e->F, 4) <= 64 * 1024;
     e->multi = lane_ok && ffm::core_multi_smem_bytes(H, W, e->F, 4) <= 64 * 1024;
-    e->lane = !e->group && (d.envs_per_block == 0 || d.envs_per_block == -2) && lane_ok &&
-              ffm::core_lane_smem_bytes(H, W, e->F, 4) <= 64 * 1024;
-    e->wave = !e->lane && !e->group && (d.envs_per_block == 0 || d.envs_per_block == -1) && A <= 64 && !e->f64 && W % 4 == 0 && EW * HW <= 512 &&
-              ffm::core_wave_smem_bytes(H, W, A, e->F, e->mt, reset_lds, 4) <= 64 * 1024;
+    const bool lane = !group && (d.envs_per_block == 0 || d.envs_per_block == -2) && lane_ok &&
+                      ffm::core_lane_smem_bytes(H, W, e->F, 4) <= 64 * 1024;
+    const bool wave = !lane && !group && (d.envs_per_block == 0 || d.envs_per_block == -1) && A <= 64 && !e->f64 && W % 4 == 0 && EW * HW <= 512 &&
+                      ffm::core_wave_smem_bytes(H, W, A, e->F, e->mt, reset_lds, 4) <= 64 * 1024;
     e->block = A > 256 ? 512 : 256;
     if (const char* bs = getenv("FFM_BLOCK_BS"))     // A/B switch: the block kernel's workgroup size
         if (atoi(bs) == 256 || atoi(bs) == 512) e->block = atoi(bs);
@@ -452,15 +479,12 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
     // Maps whose env state exceeds the LDS, or whose padded cell indices exceed u16:
     // the block kernel keeps grid, DFF tile, cell lists and placement keys in a
     // global scratch region per block (one env per block).
-    e->big = !e->wave && !e->lane && !e->group &&
+    e->big = !wave && !lane && !group &&
              ((size_t)(H + 2) * (W + 2) > 65535 ||
               ffm::core_block_smem_bytes(H, W, A, K, e->F, e->f64, e->mt, reset_lds) > 64 * 1024);
     if (e->big) e->K = 1;
     // Philox placement of the whole free list in the wave reset's LDS, else by blocks
-    auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t wave_reset_lds = al16(8 * (size_t)std::max(1, e->F)) + al16(2 * (size_t)std::max(1, d.n_agents)) +
-                                  al16(2 * (size_t)std::max(1, e->F));   // launch_core_reset's carve
-    e->block_reset = !e->mt && wave_reset_lds > 64 * 1024;
+    e->block_reset = !e->mt && wave_reset_lds(e->F, d.n_agents) > 64 * 1024;
 
     const size_t E = (size_t)d.n_envs;
     const int PW = W + 2, PHW = (H + 2) * PW;
@@ -486,7 +510,7 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
     ALLOC(e->d_sff, sff_bytes);
     ALLOC(e->d_free, std::max<size_t>(1, fl.size()) * 2);
     ALLOC(e->d_free_padded, std::max<size_t>(1, fl.size()) * 2);
-    if (e->group) {
+    if (group) {
         e->stage_bytes = ffm::core_group_stage_bytes(H, W, e->F);
         e->stage_q4 = ffm::core_group_stage_q4(H, W, e->F);
         ALLOC(e->d_stage, e->stage_bytes);
@@ -506,61 +530,41 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
         e->scratch_stride = (ffm::core_big_scratch_bytes(H, W, A, e->F, e->mt) + 255) & ~(size_t)255;
         ALLOC(e->d_scratch, E * e->scratch_stride);
     }
-    // Grids.  Persistent wave and lane kernels: CUs x resident blocks per CU.
-    int cus = 0;
-    he = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d.device);
+    // The create plan.  Persistent wave, lane and multi-step kernels: CUs x resident blocks per CU.
+    he = hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, d.device);
     if (he != hipSuccess) return cleanup(fail(FFM_E_HIP, "hipDeviceGetAttribute"));
-    size_t shard_slots = 0;   // counter slots of the step shards, one range each
     {
-        ffm::CoreStepArgs a{};
-        a.H = H; a.W = W; a.A = A; a.F = e->F; a.auto_reset = reset_lds;
-        if (e->wave) {
-            const int per_cu = std::max(1, ffm::core_wave_blocks_per_cu(a, d.neighborhood, e->mt));
-            const long long groups = (d.n_envs + EW - 1) / EW;
-            e->wave_blocks = (int)std::min<long long>((groups + 3) / 4, (long long)cus * per_cu);
-            if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {   // diagnostic override of the grid
-                const long long v = std::atoll(ov);
-                if (v > 0) e->wave_blocks = (int)std::min<long long>(v, (groups + 3) / 4);
-            }
-        }
-        if (e->lane) e->lane_blocks = lane_grid(a, d.neighborhood, d.n_envs, cus);
-        if (e->multi) {
-            const int per_cu = std::max(1, ffm::core_multi_blocks_per_cu(a, d.neighborhood));
-            const long long pairs = (d.n_envs + 1) / 2;
-            e->multi_blocks = (int)std::max<long long>(1, std::min<long long>((pairs + 3) / 4, (long long)cus * per_cu));
-            if (const char* ov = std::getenv("FFM_WAVE_BLOCKS")) {   // diagnostic override of the grid
-                const long long v = std::atoll(ov);
-                if (v > 0) e->multi_blocks = (int)std::min<long long>(v, (pairs + 3) / 4);
-            }
-        }
-        if (e->group) {
+        const ffm::CoreStepArgs a = form_args(e, e->F);
+        if (group) {
             // FFM_GROUP_ONE=0|1 (A/B and test switch, read at create): 0 keeps the loop form of
             // the group kernel on every grid; unset or 1, a launch whose waves step at most one
             // group each takes the single-group form (core_group.hip, ONE)
-            if (const char* ov = std::getenv("FFM_GROUP_ONE")) e->group_one = std::atoi(ov) != 0;
-            GroupGeom gg = group_geometry(a, d.neighborhood, d.n_envs, cus);
-            e->group_g = gg.g;
-            e->group_blocks = gg.blocks;
-            e->shards = std::move(gg.shards);
-            shard_slots = gg.shard_slots;
+            const char* ov = std::getenv("FFM_GROUP_ONE");
+            e->create_plan = group_plan(e, a, e->d_stage, !ov || std::atoi(ov) != 0);
+        } else if (lane) {
+            e->create_plan = simple_plan(e, StepPlan::kLane, lane_grid(e, a));
+        } else if (wave) {
+            e->create_plan = simple_plan(e, StepPlan::kWave,
+                                         persistent_grid((d.n_envs + EW - 1) / EW, e->cus,
+                                                         ffm::core_wave_blocks_per_cu(a, d.neighborhood, e->mt)));
+        } else {
+            e->create_plan = simple_plan(e, StepPlan::kBlock, block_grid(e));
         }
+        if (e->multi)
+            e->multi_blocks = persistent_grid((d.n_envs + 1) / 2, e->cus, ffm::core_multi_blocks_per_cu(a, d.neighborhood));
     }
-    // One counter slot per wave (wave / lane kernel) or block (block kernel):
+    // One counter slot per wave (wave / lane / group kernel) or block (block kernel):
     // summed by ffm_engine_get_counters, never contended on the device.
     {
         const long long groups = (d.n_envs + EW - 1) / EW;
         const long long blocks = (d.n_envs + K - 1) / K;
-        e->ctr_slots = (size_t)std::max<long long>(std::max<long long>(std::max<long long>(1, blocks),
-                                                                       (groups + 3) / 4 * 4),
-                                                   (long long)std::max(std::max(e->lane_blocks, e->group_blocks), e->multi_blocks) * 4);
-        e->ctr_slots = std::max(e->ctr_slots, shard_slots);
+        e->ctr_slots = (size_t)std::max<long long>(std::max<long long>(std::max<long long>(1, blocks), (groups + 3) / 4 * 4),
+                                                   (long long)e->multi_blocks * 4);
+        e->ctr_slots = std::max(e->ctr_slots, plan_slots(e->create_plan));
     }
     // the shards' streams (shard 0 runs on the caller's) and the fork / join events
-    if (!e->shards.empty()) {
-        he = ensure_shard_streams(e, e->shards.size());
-        if (he != hipSuccess)
-            return cleanup(fail(FFM_E_HIP, std::string("step shard streams: ") + hipGetErrorString(he)));
-    }
+    he = ensure_shard_streams(e, e->create_plan.shards.size());
+    if (he != hipSuccess) return cleanup(fail(FFM_E_HIP, std::string("step shard streams: ") + hipGetErrorString(he)));
     ALLOC(e->d_ctr, e->ctr_slots * 32);
     ALLOC(e->d_dbg, 16 * 8);
     if (e->mt) {
@@ -573,15 +577,9 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
         he = hipMemcpy(e->d_sff, e->f64 ? (const void*)psff64.data() : (const void*)psff32.data(), sff_bytes,
                        hipMemcpyHostToDevice);
     if (he == hipSuccess && !fl.empty()) he = hipMemcpy(e->d_free, fl.data(), fl.size() * 2, hipMemcpyHostToDevice);
-    if (he == hipSuccess && !fl.empty()) {
-        std::vector<uint16_t> fp(fl.size());
-        for (size_t i = 0; i < fl.size(); i++) fp[i] = (uint16_t)((fl[i] / W + 1) * PW + fl[i] % W + 1);
-        he = hipMemcpy(e->d_free_padded, fp.data(), fp.size() * 2, hipMemcpyHostToDevice);
-    }
-    if (he == hipSuccess && e->group) {
+    if (he == hipSuccess && !fl.empty()) he = hipMemcpy(e->d_free_padded, fp.data(), fp.size() * 2, hipMemcpyHostToDevice);
+    if (he == hipSuccess && group) {
         // the map, the SFF term, k_S and the free list have no setter: the image is final
-        std::vector<uint16_t> fp(fl.size());
-        for (size_t i = 0; i < fl.size(); i++) fp[i] = (uint16_t)((fl[i] / W + 1) * PW + fl[i] % W + 1);
         std::vector<unsigned char> img(e->stage_bytes);
         ffm::core_group_stage_build(H, W, e->F, pmap.data(), psff32.data(), e->kS32, fp.data(), img.data());
         he = hipMemcpy(e->d_stage, img.data(), img.size(), hipMemcpyHostToDevice);
@@ -639,7 +637,7 @@ static ffm::CoreStepArgs make_args(ffm_engine* e) {
     a.free_padded = e->d_free_padded;
     a.F = rooms_on(e) ? e->room_fmax : e->F;   // per-env rooms: the largest room's (the LDS sizes)
     a.reset_thr = e->reset_thr;
-    a.stage = pep_group_on(e) ? e->d_stage_raw : e->d_stage;   // the per-env form takes k_S from the records
+    a.stage = plan(e).stage;   // (the group kernel's per-env form: the image that leaves k_S to the records)
     a.stage_q4 = e->stage_q4;
     a.mt_np = e->d_mt_np;
     a.mt_py = e->d_mt_py;
@@ -663,11 +661,11 @@ static ffm::CoreStepArgs make_args(ffm_engine* e) {
 // Shards a step(n > 1) call runs as, under the engine's current settings: 1 (one launch per
 // step over all envs) with trajectory capture on (its kernel follows every step launch on the
 // caller's stream), on the fused multi-step path and with per-env parameters on the lane kernel
-// (the shards belong to the group kernel; on its per-env form they are that form's own).
+// (only plans of the group kernel hold shards; its per-env and room forms hold their own).
 static int shards_in_effect(const ffm_engine* e) {
-    const std::vector<ffm_engine::Shard>& sh = shards_now(e);
-    if (sh.size() <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi && !rooms_on(e)) || !steps_group(e)) return 1;
-    return (int)sh.size();
+    const size_t S = plan(e).shards.size();
+    if (S <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi && !rooms_on(e))) return 1;
+    return (int)S;
 }
 
 // n_steps steps as one launch per step and shard.  One fork and one join per call: the shard
@@ -677,8 +675,8 @@ static int shards_in_effect(const ffm_engine* e) {
 // of that shard only (envs are independent, every draw is keyed by (t, global env)).  Whatever
 // else the engine enqueues uses the caller's stream and is ordered by the join.
 static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
-    const std::vector<ffm_engine::Shard>& shards = shards_now(e);
-    const size_t S = shards.size();
+    const StepPlan& p = plan(e);
+    const size_t S = p.shards.size();
     const int A = e->d.agent_capacity;
     HIP_TRY(hipEventRecord(e->sh_fork, s));
     for (size_t k = 1; k < S; k++) HIP_TRY(hipStreamWaitEvent(e->sh_stream[k - 1], e->sh_fork, 0));
@@ -687,7 +685,7 @@ static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
     int done = 0;
     for (; done < n_steps && he == hipSuccess; done++) {
         for (size_t k = 0; k < S && he == hipSuccess; k++) {
-            const ffm_engine::Shard& sh = shards[k];
+            const StepPlan::Shard& sh = p.shards[k];
             ffm::CoreStepArgs a = base;
             a.t = e->t + (uint32_t)done;
             a.E = sh.n;
@@ -701,7 +699,7 @@ static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
             if (base.room_of_env) a.room_of_env = base.room_of_env + sh.e0;
             a.counters = base.counters + 4 * sh.ctr0;
             a.no_step_count = k != 0;   // one shard per step counts the step
-            he = ffm::launch_core_group(a, e->d.neighborhood, sh.blocks, k ? e->sh_stream[k - 1] : s, sh.g, e->group_one);
+            he = ffm::launch_core_group(a, e->d.neighborhood, sh.blocks, k ? e->sh_stream[k - 1] : s, sh.g, p.one);
         }
     }
     // the join also after a failed launch: what was enqueued stays ordered before the caller's next work
@@ -741,12 +739,15 @@ int ffm_engine_step(ffm_engine* e, int32_t n_steps, void* stream) {
         }
         if (cs == hipStreamCaptureStatusNone) return step_sharded(e, n_steps, s);
     }
+    const StepPlan& p = plan(e);
     for (int i = 0; i < n_steps; i++) {
         ffm::CoreStepArgs a = make_args(e);
-        if (steps_group(e)) HIP_TRY(ffm::launch_core_group(a, e->d.neighborhood, group_blocks_now(e), s, group_g_now(e), e->group_one));
-        else if (steps_lane(e)) HIP_TRY(ffm::launch_core_lane(a, e->d.neighborhood, lane_blocks_now(e), s));
-        else if (steps_wave(e)) HIP_TRY(ffm::launch_core_wave(a, e->d.neighborhood, e->mt, e->wave_blocks, s));
-        else HIP_TRY(ffm::launch_core_block(a, e->d.neighborhood, e->f64, e->mt, e->block, s));
+        switch (p.kernel) {
+        case StepPlan::kGroup: HIP_TRY(ffm::launch_core_group(a, e->d.neighborhood, p.blocks, s, p.g, p.one)); break;
+        case StepPlan::kLane: HIP_TRY(ffm::launch_core_lane(a, e->d.neighborhood, p.blocks, s)); break;
+        case StepPlan::kWave: HIP_TRY(ffm::launch_core_wave(a, e->d.neighborhood, e->mt, p.blocks, s)); break;
+        case StepPlan::kBlock: HIP_TRY(ffm::launch_core_block(a, e->d.neighborhood, e->f64, e->mt, e->block, s)); break;
+        }
         if (e->cap.n_sel) HIP_TRY(ffm::launch_core_capture(a, e->cap, s));
         e->t++;
     }
@@ -1078,10 +1079,7 @@ static ffm::EnvParams env_record(const ffm_env_params& q, int nb, int F) {
     r.c0 = (float)((1.0 - q.decay) * (1.0 - q.diffuse));
     r.c1 = (float)(q.decay * (1.0 - q.diffuse) / (double)nb);
     r.N = q.n_agents;
-    const int N = q.n_agents;
-    int M = std::min(F, N + std::max(8, (N + 1) / 2));
-    if (const char* ov = std::getenv("FFM_RESET_CANDIDATES")) M = std::max(0, std::min(F, std::atoi(ov)));
-    r.reset_thr = M == 0 ? 0u : M == F ? 0xFFFFFFFFu : (uint32_t)(((uint64_t)M << 32) / (uint64_t)F);
+    r.reset_thr = placement_threshold(q.n_agents, F);
     return r;
 }
 
@@ -1116,11 +1114,20 @@ static long long env_over_capacity(const ffm_engine* e, const ffm_env_params* se
     return -1;
 }
 
+// Rewrites every env's record on stream s, after the steps queued there (which may still read the
+// old ones), and waits for it (the off-paths of one feature while the other stays on).
+static int rewrite_records(ffm_engine* e, const std::vector<ffm::EnvParams>& rec, hipStream_t s) {
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(e->d_envp, rec.data(), rec.size() * sizeof(ffm::EnvParams), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return FFM_OK;
+}
+
 // What the group kernel's per-env form needs beyond the records: its stage image (built once:
 // the create-time image with the SFF term's multiplier 1, so the LDS region holds the raw SFF) and
-// its launch geometry, sized from that form's occupancy (envp: any non-null pointer, it only
-// selects the form).  Fills the pep_group_* fields; the caller sets pep_group.
-static int pep_group_setup(ffm_engine* e, const ffm::EnvParams* envp) {
+// its plan, sized from that form's occupancy (envp: any non-null pointer, it only selects the
+// form).  The caller commits *out to pep_group_plan.
+static int pep_group_setup(ffm_engine* e, const ffm::EnvParams* envp, StepPlan* out) {
     const int H = e->d.H, W = e->d.W, PHW = (H + 2) * (W + 2);
     HIP_TRY(hipSetDevice(e->d.device));
     if (!e->d_stage_raw) {
@@ -1141,39 +1148,32 @@ static int pep_group_setup(ffm_engine* e, const ffm::EnvParams* envp) {
         }
         e->d_stage_raw = buf;
     }
-    int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->d.device));
-    ffm::CoreStepArgs a{};
-    a.H = H; a.W = W; a.A = e->d.agent_capacity; a.F = e->F; a.auto_reset = e->d.auto_reset;
-    a.envp = envp;   // the occupancy of the per-env form
-    GroupGeom gg = group_geometry(a, e->d.neighborhood, e->d.n_envs, cus);
+    StepPlan p = group_plan(e, form_args(e, e->F, envp), e->d_stage_raw, e->create_plan.one);
     // The counter slots were sized at create.  A geometry that needs more (the per-env form
     // resident in other numbers than the create-time form, so another group size or shard count)
     // gives way to the create-time one, which is valid for every form.
-    if (std::max((size_t)gg.blocks * 4, gg.shard_slots) > e->ctr_slots) {
-        gg.g = e->group_g;
-        gg.blocks = e->group_blocks;
-        gg.shards = e->shards;
+    if (plan_slots(p) > e->ctr_slots) {
+        p = e->create_plan;
+        p.stage = e->d_stage_raw;
     }
-    const hipError_t he = ensure_shard_streams(e, gg.shards.size());
+    const hipError_t he = ensure_shard_streams(e, p.shards.size());
     if (he != hipSuccess) return fail(FFM_E_HIP, std::string("step shard streams: ") + hipGetErrorString(he));
-    e->pep_group_g = gg.g;
-    e->pep_group_blocks = gg.blocks;
-    e->pep_shards = std::move(gg.shards);
+    *out = std::move(p);
     return FFM_OK;
 }
 
 int ffm_engine_set_env_params_kernel(ffm_engine* e, int32_t mode) {
     if (!e) return fail(FFM_E_INVALID, "null engine");
     if (mode != 0 && mode != 1) return fail(FFM_E_INVALID, "env params kernel: mode must be 0 (lane) or 1 (group)");
-    if (mode == 1 && (!e->group || e->mt))
+    if (mode == 1 && (!created_on(e, StepPlan::kGroup) || e->mt))
         return fail(FFM_E_UNSUPPORTED, "env params kernel: the engine was not created on the group kernel");
-    if (mode == 1 && pep_on(e) && !e->pep_group) {   // the feature is on: move it now
-        const int rc = pep_group_setup(e, e->d_envp);
+    if (mode == 1 && pep_on(e) && e->pep_kernel != 1) {   // the feature is on: move it now
+        StepPlan p;
+        const int rc = pep_group_setup(e, e->d_envp, &p);
         if (rc) return rc;
+        e->pep_group_plan = std::move(p);
     }
     e->pep_kernel = mode;
-    e->pep_group = mode == 1 && pep_on(e);
     return FFM_OK;
 }
 
@@ -1188,10 +1188,8 @@ int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t
         if (rooms_on(e)) {   // the rooms keep a record per env: the create-time values, each room's threshold
             if (env_over_capacity(e, nullptr, nullptr, &e->room_f, e->room_of_env.data()) >= 0)
                 return fail(FFM_E_INVALID, "env params: the create-time n_agents exceeds the free cells of an env's room");
-            const std::vector<ffm::EnvParams> rec = env_records(e, nullptr, nullptr, &e->room_f, e->room_of_env.data());
-            HIP_TRY(hipStreamSynchronize(s));
-            HIP_TRY(hipMemcpyAsync(e->d_envp, rec.data(), rec.size() * sizeof(ffm::EnvParams), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipStreamSynchronize(s));
+            const int rc = rewrite_records(e, env_records(e, nullptr, nullptr, &e->room_f, e->room_of_env.data()), s);
+            if (rc) return rc;
         } else {
             HIP_TRY(hipStreamSynchronize(s));        // queued steps may still read the records
             (void)hipFree(e->d_envp);
@@ -1199,14 +1197,11 @@ int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t
         }
         e->pep_sets.clear();
         e->pep_set_of_env.clear();
-        e->pep_lane = false;
-        e->pep_lane_blocks = 0;
-        e->pep_group = false;
-        e->pep_shards.clear();
+        e->pep_plan = e->pep_group_plan = StepPlan{};
         return FFM_OK;
     }
     if (!sets || !set_of_env) return fail(FFM_E_INVALID, "env params: sets and set_of_env are required");
-    const int A = e->d.agent_capacity, nb = e->d.neighborhood;
+    const int A = e->d.agent_capacity;
     for (int32_t p = 0; p < n_sets; p++) {
         const ffm_env_params& q = sets[p];
         if (!std::isfinite(q.k_S) || !std::isfinite(q.k_D) || !std::isfinite(q.diffuse) || !std::isfinite(q.decay))
@@ -1223,7 +1218,8 @@ int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t
         return fail(FFM_E_INVALID, "env params: n_agents exceeds the free cells of an env's room");
     // The kernel while on.  Group engines: the lane kernel (the group kernel's conditions include
     // the lane kernel's); wave engines, and whatever else is not on the lane kernel: the block kernel.
-    const bool lane = e->lane || (e->group && ffm::core_lane_smem_bytes(e->d.H, e->d.W, e->F, 4) <= 64 * 1024);
+    const bool lane = created_on(e, StepPlan::kLane) ||
+                      (created_on(e, StepPlan::kGroup) && ffm::core_lane_smem_bytes(e->d.H, e->d.W, e->F, 4) <= 64 * 1024);
     if (!lane && !e->big &&
         ffm::core_block_smem_bytes(e->d.H, e->d.W, A, e->K, e->F, e->f64, false, e->d.auto_reset != 0) +
                 ffm::core_block_pep_smem_bytes(e->K) > 64 * 1024)
@@ -1231,7 +1227,6 @@ int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t
     // The records, with the expressions of ffm_engine_create (the same bits as a homogeneous engine)
     const std::vector<ffm::EnvParams> rec = env_records(e, sets, set_of_env, room_f, e->room_of_env.data());
     HIP_TRY(hipSetDevice(e->d.device));
-    int lane_blocks = 0;
     ffm::EnvParams* buf = e->d_envp;   // (per-env rooms: the engine's own records are there already)
     if (!buf) {
         hipError_t he = hipMalloc((void**)&buf, E * sizeof(ffm::EnvParams));
@@ -1241,19 +1236,14 @@ int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t
         if (!e->d_envp) (void)hipFree(buf);
         return rc;
     };
-    if (lane) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->d.device) != hipSuccess)
-            return undo(fail(FFM_E_HIP, "hipDeviceGetAttribute"));
-        ffm::CoreStepArgs a{};
-        a.H = e->d.H; a.W = e->d.W; a.A = A; a.F = e->F; a.auto_reset = e->d.auto_reset;
-        a.envp = buf;   // the occupancy of the per-env form
-        lane_blocks = lane_grid(a, nb, e->d.n_envs, cus);
-    }
-    // the group kernel's own per-env form, if that is the engine's setting
-    const bool to_group = e->pep_kernel == 1 && e->group;
-    if (to_group && !e->pep_group) {
-        const int rc = pep_group_setup(e, buf);
+    // the occupancy of the per-env form (buf: any non-null pointer selects it)
+    StepPlan pp = lane ? simple_plan(e, StepPlan::kLane, lane_grid(e, form_args(e, e->F, buf)))
+                       : simple_plan(e, StepPlan::kBlock, block_grid(e));
+    // the group kernel's own per-env form, if that is the engine's setting and the feature is not on it yet
+    const bool to_group = e->pep_kernel == 1 && !pep_on(e);
+    StepPlan gp;
+    if (to_group) {
+        const int rc = pep_group_setup(e, buf, &gp);
         if (rc) return undo(rc);
     }
     // stream-ordered after the steps queued so far; the tables are consumed before the return
@@ -1263,9 +1253,8 @@ int ffm_engine_set_env_params(ffm_engine* e, const ffm_env_params* sets, int32_t
     e->d_envp = buf;
     e->pep_sets.assign(sets, sets + n_sets);
     e->pep_set_of_env.assign(set_of_env, set_of_env + E);
-    e->pep_lane = lane;
-    e->pep_lane_blocks = lane_blocks;
-    e->pep_group = to_group;
+    e->pep_plan = std::move(pp);
+    if (to_group) e->pep_group_plan = std::move(gp);
     return FFM_OK;
 }
 
@@ -1292,11 +1281,8 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
         if (pep) {   // the sets stay: their records with the create-time room's threshold again
             if (env_over_capacity(e, e->pep_sets.data(), e->pep_set_of_env.data(), nullptr, nullptr) >= 0)
                 return fail(FFM_E_INVALID, "env rooms: a parameter set's n_agents exceeds the create-time room's free cells");
-            const std::vector<ffm::EnvParams> rec =
-                env_records(e, e->pep_sets.data(), e->pep_set_of_env.data(), nullptr, nullptr);
-            HIP_TRY(hipStreamSynchronize(s));        // queued steps may still read the records and tables
-            HIP_TRY(hipMemcpyAsync(e->d_envp, rec.data(), E * sizeof(ffm::EnvParams), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipStreamSynchronize(s));
+            const int rc = rewrite_records(e, env_records(e, e->pep_sets.data(), e->pep_set_of_env.data(), nullptr, nullptr), s);
+            if (rc) return rc;
         } else {
             HIP_TRY(hipStreamSynchronize(s));
             (void)hipFree(e->d_envp);
@@ -1308,11 +1294,7 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
         e->d_room_of_env = nullptr;
         e->room_stride = 0;
         e->room_fmax = 0;
-        e->room_lane_blocks = 0;
-        e->room_block = false;
-        e->room_group = false;
-        e->room_group_blocks = 0;
-        e->room_shards.clear();
+        e->room_plan = StepPlan{};
         e->room_maps.clear();
         e->room_sffs.clear();
         e->room_of_env.clear();
@@ -1334,14 +1316,7 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     std::vector<int> room_f((size_t)n_rooms);
     int fmax = 0;
     for (int32_t r = 0; r < n_rooms; r++) {
-        const uint8_t* m = maps + (size_t)r * HW;
-        for (int i = 0; i < HW; i++) {
-            const int x = i / W, y = i % W;
-            if (m[i] != 0) continue;
-            if (x == 0 || y == 0 || x == H - 1 || y == W - 1)
-                return fail(FFM_E_INVALID, "free cell on the map border (walls must enclose the room)");
-            fp[(size_t)r].push_back((uint16_t)((x + 1) * PW + y + 1));
-        }
+        if (!scan_free(maps + (size_t)r * HW, H, W, &fp[(size_t)r])) return fail(FFM_E_INVALID, kBorderError);
         room_f[(size_t)r] = (int)fp[(size_t)r].size();
         fmax = std::max(fmax, room_f[(size_t)r]);
     }
@@ -1358,13 +1333,11 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
                 ffm::core_block_room_smem_bytes(e->K) > 64 * 1024)
             return fail(FFM_E_UNSUPPORTED, "env rooms: the block kernel's LDS has no room for the largest room and the K records");
         // the placement of the largest room: in the block reset's scratch (sized at create), or in
-        // the wave reset's LDS (launch_core_reset's carve)
-        auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+        // the wave reset's LDS
         if (e->block_reset ? ffm::core_big_scratch_bytes(H, W, e->d.agent_capacity, fmax, false) > e->scratch_stride
-                           : al16(8 * (size_t)std::max(1, fmax)) + al16(2 * (size_t)e->d.agent_capacity) +
-                                     al16(2 * (size_t)std::max(1, fmax)) > 64 * 1024)
+                           : wave_reset_lds(fmax, e->d.agent_capacity) > 64 * 1024)
             return fail(FFM_E_UNSUPPORTED, "env rooms: the placement has no room for the largest room's free list");
-        if ((size_t)((e->d.n_envs + e->K - 1) / e->K) > e->ctr_slots)
+        if ((size_t)block_grid(e) > e->ctr_slots)
             return fail(FFM_E_UNSUPPORTED, "env rooms: counter slots");
     }
     const ffm_env_params* sets = pep ? e->pep_sets.data() : nullptr;
@@ -1396,8 +1369,6 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     const std::vector<ffm::EnvParams> rec = env_records(e, sets, set_of_env, &room_f, room_of_env);
 
     HIP_TRY(hipSetDevice(e->d.device));
-    int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->d.device));
     unsigned char* d_rooms = nullptr;
     int32_t* d_roe = nullptr;
     ffm::EnvParams* d_envp = nullptr;
@@ -1415,8 +1386,9 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     if (he == hipSuccess) he = hipMalloc((void**)&d_roe, roe_bytes);
     if (he == hipSuccess) he = hipMalloc((void**)&d_envp, E * sizeof(ffm::EnvParams));
     if (he != hipSuccess) return undo(fail(FFM_E_NOMEM, std::string("env rooms: ") + hipGetErrorString(he)));
-    int lane_blocks = 0;
-    GroupGeom rg;
+    // The room plan, from the occupancy of the room form (the tables select it).
+    const ffm::CoreStepArgs fa = form_args(e, fmax, d_envp, d_rooms, d_roe);
+    StepPlan rp;
     size_t ctr_slots = e->ctr_slots;
     if (group_form) {
         // The group kernel's room form: envs per group and step shards from that form's occupancy, as
@@ -1424,24 +1396,20 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
         // adds to one counter slot per wave of its grid, so a geometry with more waves than the slots
         // allocated at create gets a larger array, the sums carried over (below): the create-time
         // kernels keep their arguments and resources.
-        ffm::CoreStepArgs a{};
-        a.H = H; a.W = W; a.A = e->d.agent_capacity; a.F = fmax; a.auto_reset = e->d.auto_reset;
-        a.envp = d_envp; a.rooms = d_rooms; a.room_of_env = d_roe;   // the occupancy of the room form
-        rg = group_geometry(a, e->d.neighborhood, e->d.n_envs, cus, true);
-        ctr_slots = std::max(ctr_slots, std::max((size_t)rg.blocks * 4, rg.shard_slots));
+        rp = group_plan(e, fa, e->d_stage, true);
+        ctr_slots = std::max(ctr_slots, plan_slots(rp));
         if (ctr_slots > e->ctr_slots) {
             he = hipMalloc((void**)&d_ctr, ctr_slots * 32);
             if (he != hipSuccess) return undo(fail(FFM_E_NOMEM, std::string("env rooms: counters: ") + hipGetErrorString(he)));
         }
-        he = ensure_shard_streams(e, rg.shards.size());
+        he = ensure_shard_streams(e, rp.shards.size());
         if (he != hipSuccess) return undo(fail(FFM_E_HIP, std::string("step shard streams: ") + hipGetErrorString(he)));
-    } else if (!block_form) {
-        ffm::CoreStepArgs a{};
-        a.H = H; a.W = W; a.A = e->d.agent_capacity; a.F = fmax; a.auto_reset = e->d.auto_reset;
-        a.envp = d_envp; a.rooms = d_rooms; a.room_of_env = d_roe;   // the occupancy of the room form
-        lane_blocks = lane_grid(a, e->d.neighborhood, e->d.n_envs, cus);
+    } else if (block_form) {
+        rp = simple_plan(e, StepPlan::kBlock, block_grid(e));
+    } else {
+        rp = simple_plan(e, StepPlan::kLane, lane_grid(e, fa));
+        if (plan_slots(rp) > e->ctr_slots) return undo(fail(FFM_E_UNSUPPORTED, "env rooms: counter slots"));
     }
-    if ((size_t)lane_blocks * 4 > e->ctr_slots) return undo(fail(FFM_E_UNSUPPORTED, "env rooms: counter slots"));
     // stream-ordered after the steps queued so far; the tables are consumed before the return
     he = hipStreamSynchronize(s);
     if (he == hipSuccess) he = hipMemsetAsync(d_roe, 0, roe_bytes, s);
@@ -1465,12 +1433,7 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     e->d_envp = d_envp;
     e->room_stride = lay.stride;
     e->room_fmax = fmax;
-    e->room_lane_blocks = lane_blocks;
-    e->room_block = block_form;
-    e->room_group = group_form;
-    e->room_group_g = rg.g;
-    e->room_group_blocks = rg.blocks;
-    e->room_shards = std::move(rg.shards);
+    e->room_plan = std::move(rp);
     e->room_maps.assign(maps, maps + (size_t)n_rooms * HW);
     e->room_sffs.assign(sffs, sffs + (size_t)n_rooms * HW);
     e->room_of_env.assign(room_of_env, room_of_env + E);
@@ -1483,13 +1446,13 @@ int ffm_engine_set_env_rooms_kernel(ffm_engine* e, int32_t mode) {
     if (mode != 0 && mode != 1 && mode != 2)
         return fail(FFM_E_INVALID, "env rooms kernel: mode must be 0 (lane), 1 (block) or 2 (group)");
     if (rooms_on(e)) return fail(FFM_E_INVALID, "env rooms kernel: rooms are on (turn them off first)");
-    if (mode == 2 && (!e->group || e->mt || e->f64))
+    if (mode == 2 && (!created_on(e, StepPlan::kGroup) || e->mt || e->f64))
         return fail(FFM_E_UNSUPPORTED, "env rooms kernel: the engine was not created on the group kernel (12x12, "
                                        "agent_capacity <= 32, Philox, float32 SFF)");
     if (mode == 1) {
         if (e->mt) return fail(FFM_E_UNSUPPORTED, "env rooms kernel: Philox engines only");
         if (e->f64) return fail(FFM_E_UNSUPPORTED, "env rooms kernel: float32-SFF engines only");
-        if (e->lane || e->group)
+        if (created_on(e, StepPlan::kLane) || created_on(e, StepPlan::kGroup))
             return fail(FFM_E_UNSUPPORTED, "env rooms kernel: lane and group engines have the lane kernel's room form");
         if (e->big)
             return fail(FFM_E_UNSUPPORTED, "env rooms kernel: engines with their state in global scratch (block_scratch) "
@@ -1574,13 +1537,18 @@ int ffm_debug_stage_image(ffm_engine* e, void* out, int64_t cap, int64_t* n) {
 int ffm_debug_group_occupancy(ffm_engine* e, int32_t one, int32_t* blocks_per_cu) {
     if (!e || !blocks_per_cu) return fail(FFM_E_INVALID, "bad args");
     *blocks_per_cu = 0;
-    if (!e->group) return FFM_OK;
+    if (!created_on(e, StepPlan::kGroup)) return FFM_OK;
     HIP_TRY(hipSetDevice(e->d.device));
     ffm::CoreStepArgs a = make_args(e);
-    // the form that steps the engine (the per-env one, or the room form, only while it does)
-    if (!pep_group_on(e) && !room_group_on(e)) a.envp = nullptr;
-    if (!room_group_on(e)) a.rooms = nullptr;
-    *blocks_per_cu = ffm::core_group_blocks_per_cu(a, e->d.neighborhood, group_g_now(e), one != 0);
+    // the form that steps the engine; while another kernel does (per-env parameters or rooms on
+    // the lane kernel), the create-time form at the create-time group size
+    const StepPlan* p = &plan(e);
+    if (p->kernel != StepPlan::kGroup) {
+        p = &e->create_plan;
+        a.envp = nullptr;
+        a.rooms = nullptr;
+    }
+    *blocks_per_cu = ffm::core_group_blocks_per_cu(a, e->d.neighborhood, p->g, one != 0);
     return FFM_OK;
 }
 
@@ -1592,8 +1560,8 @@ int ffm_debug_reset_candidates(ffm_engine* e, int32_t* m, uint32_t* thr) {
     return FFM_OK;
 }
 
-// Diagnostic (not part of the ABI header): the launch geometry in effect (chosen at create; with
-// per-env parameters on, the kernel, grid and shards that step the engine meanwhile).
+// Diagnostic (not part of the ABI header): the step plan in effect (plan(): the create plan, or with
+// per-env parameters or rooms on, the kernel, grid and shards that step the engine meanwhile).
 //   out[0] step kernel (0 group, 1 lane, 2 wave, 3 block, 4 block with global scratch)
 //   out[1] envs per group of the group kernel (0 for the other kernels)
 //   out[2] blocks of the step kernel's grid
@@ -1607,29 +1575,25 @@ int ffm_debug_reset_candidates(ffm_engine* e, int32_t* m, uint32_t* thr) {
 //          for the other kernels)
 int ffm_debug_launch_info(ffm_engine* e, int32_t* out, int n) {
     if (!e || !out || n < 0 || n > 10) return fail(FFM_E_INVALID, "bad args");
-    const bool group = steps_group(e), lane = steps_lane(e), wave = steps_wave(e);
-    const int kernel = group ? 0 : lane ? 1 : wave ? 2 : e->big ? 4 : 3;
-    const long long E = e->d.n_envs;
+    const StepPlan& p = plan(e);
+    const bool block = p.kernel == StepPlan::kBlock;
     const int S = shards_in_effect(e);
-    const int32_t step_blocks = group ? group_blocks_now(e) : lane ? lane_blocks_now(e) : wave ? e->wave_blocks
-                                                                                        : (int32_t)((E + e->K - 1) / e->K);
-    bool one = group && e->group_one;
-    if (room_group_on(e)) one = true;   // the room form is the single-group form on every grid
-    else if (one && S > 1) {
-        for (const ffm_engine::Shard& sh : shards_now(e)) one = one && ffm::core_group_one_group(sh.n, sh.blocks, sh.g);
+    bool one = p.kernel == StepPlan::kGroup && p.one;
+    if (one && S > 1) {
+        for (const StepPlan::Shard& sh : p.shards) one = one && ffm::core_group_one_group(sh.n, sh.blocks, sh.g);
     } else if (one) {
-        one = ffm::core_group_one_group(E, group_blocks_now(e), group_g_now(e));
+        one = ffm::core_group_one_group(e->d.n_envs, p.blocks, p.g);
     }
     const int32_t v[10] = {
-        kernel,
-        group ? group_g_now(e) : 0,
-        step_blocks,
+        block && e->big ? 4 : (int32_t)p.kernel,
+        p.g,
+        p.blocks,
         e->K,
-        kernel <= 2 ? 256 : e->big ? 1024 : e->block,
+        !block ? 256 : e->big ? 1024 : e->block,
         e->multi ? 1 : 0,
         e->multi ? e->multi_blocks : 0,
         S,
-        S > 1 ? shards_now(e)[0].blocks : step_blocks,
+        S > 1 ? p.shards[0].blocks : p.blocks,
         one ? 1 : 0,
     };
     for (int i = 0; i < n; i++) out[i] = v[i];

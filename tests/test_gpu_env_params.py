@@ -14,12 +14,13 @@ import functools
 import numpy as np
 import pytest
 
+from env_sweep_util import _assert_same, _dicts, _params, _snapshot
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 SEED = 42
-KEYS = ("k_S", "k_D", "diffuse", "decay", "n_agents")
 # the 12x12 sets (k_S, k_D, diffuse, decay, N); env e runs set e % 5
 SETS5 = ((3, 1, 0.2, 0.2, 32), (0.5, 0, 0.2, 0.2, 5), (10, 2.5, 0.05, 0.6, 17), (1.5, 1, 0.5, 0.1, 1),
          (1, 4, 0.3, 0.3, 24))
@@ -38,26 +39,11 @@ def _gpu():
     torch.cuda.init()
 
 
-def _dicts(sets):
-    return [dict(zip(KEYS, s)) for s in sets]
-
-
-def _params(s, nbh):
-    return {"k_S": s[0], "k_D": s[1], "diffuse": s[2], "decay": s[3], "neighborhood": nbh}
-
-
 @functools.lru_cache(maxsize=None)
 def _room(H, W, f64=False):
     from ffm_amd.data import make_room, l1_sff
     m = make_room(H, W)
     return m, l1_sff(m, dtype=np.float64 if f64 else np.float32)
-
-
-def _episodes(eng):
-    from ffm_amd.engine import _DevArray
-    torch.cuda.synchronize()
-    ptr = eng.device_buffers()["episodes"]
-    return torch.as_tensor(_DevArray(ptr, eng.n_envs, "<i4"), device=f"cuda:{eng.device}").cpu().numpy().copy()
 
 
 # ---------------------------------------------------------------------------
@@ -131,24 +117,6 @@ def _engine(H, W, A, nbh, E, create, epb=0, f64=False, env_base=0, rng="philox")
     m, s = _room(H, W, f64)
     return Engine(m, s, n_envs=E, n_agents=create[4], agent_capacity=A, params=_params(create, nbh), rng=rng,
                   seed=SEED, auto_reset=True, env_base=env_base, envs_per_block=epb)
-
-
-def _snapshot(eng):
-    pos, cnt, dff = eng.get_state()
-    c = eng.counters()
-    return {"pos": pos, "cnt": cnt, "dff": dff, "eps": _episodes(eng), "agent_steps": c["agent_steps"],
-            "resets": c["resets"]}
-
-
-def _assert_same(got, want, what=""):
-    assert np.array_equal(got["cnt"], want["cnt"]), f"{what}: counts differ"
-    assert np.array_equal(got["eps"], want["eps"]), f"{what}: episodes differ"
-    for e in range(len(want["cnt"])):
-        n = want["cnt"][e]
-        assert np.array_equal(got["pos"][e, :n], want["pos"][e, :n]), f"{what}: positions differ (env {e})"
-    assert np.array_equal(got["dff"].view(np.uint32), want["dff"].view(np.uint32)), f"{what}: DFF bits differ"
-    assert got["agent_steps"] == want["agent_steps"], f"{what}: agent_steps"
-    assert got["resets"] == want["resets"], f"{what}: resets"
 
 
 def _assert_resets(eps, sets, which):

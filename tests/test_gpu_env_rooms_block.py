@@ -4,8 +4,8 @@ ffm_engine_set_env_rooms_kernel): geometry sweeps for rooms beyond the lane kern
 The contract is that of tests/test_gpu_env_rooms.py: env e of an engine with
 per-env rooms evolves bit for bit like the env with the same global id of a homogeneous engine
 created with that room's map and SFF (and, with per-env parameters on as well, that env's set).
-The expected state comes from the oracle, one env at a time (the helpers below are copies of that
-file's, with the create-time N a parameter and one more op, a room change).  Every case asserts the
+The expected state comes from the oracle, one env at a time (the helpers of tests/env_sweep_util.py,
+with the create-time N a parameter).  Every case asserts the
 create-time launch_info()["kernel"], then kernel == "block" and env_rooms == R while the form is on,
 before it compares anything; every auto-reset case asserts from the oracle's result that every room
 completed an episode, so every room's own F and free list was placed from inside the step kernel.
@@ -24,16 +24,14 @@ import functools
 import numpy as np
 import pytest
 
+import env_sweep_util as U
+from env_sweep_util import SETS5, _assert_coverage, _assert_same, _dicts, _snapshot
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-SEED = 42
 PAR = (3, 1, 0.2, 0.2)                  # the create-time parameters (k_S, k_D, diffuse, decay)
-KEYS = ("k_S", "k_D", "diffuse", "decay", "n_agents")
-# the sets of tests/test_gpu_env_params.py
-SETS5 = ((3, 1, 0.2, 0.2, 32), (0.5, 0, 0.2, 0.2, 5), (10, 2.5, 0.05, 0.6, 17), (1.5, 1, 0.5, 0.1, 1),
-         (1, 4, 0.3, 0.3, 24))
 NBHS = ("neumann", "moore")
 
 # name: rooms, A, N, E, T, the create-time kernel, the first step by which every room has completed an
@@ -57,12 +55,9 @@ def _gpu():
     torch.cuda.init()
 
 
-@functools.lru_cache(maxsize=None)
-def _room(name):
-    """(map, float32 SFF) of a named room: the L1 field, or where the room has an obstacle in the
-    way (P20B, P64B) its geodesic_sff (the default, Neumann, field under both neighbourhoods)."""
-    from ffm_amd.data import geodesic_sff, l1_sff, make_room
-    geo = False
+def _map(name):
+    """The map of a named room."""
+    from ffm_amd.data import make_room
     if name == "R0":
         m = make_room(12, 12)
     elif name == "R1":                       # a 2-wide exit
@@ -94,13 +89,11 @@ def _room(name):
     elif name == "P20B":                     # a barrier in front of the exit: a trap under l1_sff
         m = make_room(20, 20)
         m[4, 5:16] = 2
-        geo = True
     elif name == "P64":
         m = make_room(64, 64)
     elif name == "P64B":
         m = make_room(64, 64, exit_pos=(0, 10), exit_width=3)
         m[20:24, 8:14] = 2
-        geo = True
     elif name == "P84":
         m = make_room(84, 84)
     elif name == "P84W":
@@ -110,10 +103,13 @@ def _room(name):
         m = make_room(128, 128)
     else:
         raise KeyError(name)
-    s = geodesic_sff(m) if geo else l1_sff(m)
-    m.setflags(write=False)
-    s.setflags(write=False)
-    return m, s
+    return m
+
+
+# name -> (map, float32 SFF): the L1 field, or where the room has an obstacle in the way its geodesic_sff
+_room = U.rooms(_map, geodesic=("P20B", "P64B"))
+# the shared helpers (env_sweep_util.py) over this file's rooms; rooms on: the block kernel, one shard
+_assert_on = functools.partial(U._assert_on, kernel="block", shards=1)
 
 
 def test_room_free_cells():
@@ -121,151 +117,22 @@ def test_room_free_cells():
     assert int((_room("P84")[0] == 0).sum()) == 6724
 
 
-def _params(s, nbh):
-    return {"k_S": s[0], "k_D": s[1], "diffuse": s[2], "decay": s[3], "neighborhood": nbh}
-
-
-def _dicts(sets):
-    return [dict(zip(KEYS, s)) for s in sets]
-
-
-def _episodes(eng):
-    from ffm_amd.engine import _DevArray
-    torch.cuda.synchronize()
-    ptr = eng.device_buffers()["episodes"]
-    return torch.as_tensor(_DevArray(ptr, eng.n_envs, "<i4"), device=f"cuda:{eng.device}").cpu().numpy().copy()
-
-
-# ---------------------------------------------------------------------------
-# The oracle mirror: one Core per (room, set), one env per call.
-# rooms: room names; roe / soe: per-env indices (tuples); sets: parameter sets, or None (PAR + (N,)).
-# ops: ("step", n) | ("snap",) | ("reset_envs", mask tuple) | ("drain",) | ("roe", new roe tuple)
-# sel: envs whose trajectory rows are mirrored.  Returns the snapshots, the episode records and,
-# per ("drain",), the rows {(env, k): (steps, [positions])} since the drain before.
-# ---------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
 def _oracle(A, N0, nbh, rooms, roe, sets, soe, ops, sel=()):
-    from oracle import oracle as O
-    E = len(roe)
-    roe = list(roe)
-    H, W = _room(rooms[0])[0].shape
-    sets = sets or (PAR + (N0,),)
-    soe = soe or (0,) * E
-    cores = {}
-
-    def core(e):
-        key = (rooms[roe[e]], sets[soe[e]][:4])
-        if key not in cores:
-            m, s = _room(key[0])
-            cores[key] = O.Core(np.array(m), np.array(s), _params(key[1], nbh))
-        return cores[key]
-
-    N = [sets[soe[e]][4] for e in range(E)]
-    pos = np.full((E, A), 0xFFFF, np.uint16)
-    cnt = np.zeros(E, np.int32)
-    dff = np.zeros((E, H, W), np.float32)
-    eps = np.zeros(E, np.int32)
-    for e in range(E):                                   # reset(): placement keyed t = 0
-        pos[e, :N[e]] = core(e).reset_philox(N[e], SEED, 0, e)
-        cnt[e] = N[e]
-    start = np.zeros(E, np.int64)
-    insteps = {e: 0 for e in sel}
-    rows, drains = {}, []
-    agent_steps, t, snaps, recs = 0, 1, [], []
-    for op in ops:
-        if op[0] == "step":
-            for _ in range(op[1]):
-                agent_steps += int(cnt.sum())
-                for e in range(E):
-                    k0 = int(eps[e])
-                    core(e).step_philox_batch(pos[e:e + 1], cnt[e:e + 1], dff[e:e + 1], eps[e:e + 1], SEED, t, True,
-                                              N[e], e, 1)
-                    ended = eps[e] != k0
-                    if ended:
-                        recs.append((e, k0, t - start[e], t))
-                        start[e] = t
-                    if e in insteps:                      # the row after this step (an ended episode: the empty row)
-                        insteps[e] += 1
-                        st, ps = rows.setdefault((e, k0), ([], []))
-                        st.append(insteps[e])
-                        cc = np.zeros(0, np.int32) if ended else pos[e, :cnt[e]].astype(np.int32)
-                        ps.append(np.stack([cc // W, cc % W], axis=1))
-                        if ended:
-                            insteps[e] = 0
-                t += 1
-        elif op[0] == "snap":
-            snaps.append({"pos": pos.copy(), "cnt": cnt.copy(), "dff": dff.copy(), "eps": eps.copy(),
-                          "agent_steps": agent_steps, "resets": int(eps.sum())})
-        elif op[0] == "reset_envs":                      # placed with index t, which advances
-            for e in np.flatnonzero(np.asarray(op[1])):
-                pos[e] = 0xFFFF
-                pos[e, :N[e]] = core(e).reset_philox(N[e], SEED, t, e)
-                cnt[e] = N[e]
-                dff[e] = 0.0
-                start[e] = t
-                if e in insteps:
-                    insteps[e] = 0
-            t += 1
-        elif op[0] == "roe":                             # a room change (the caller re-places those envs next)
-            roe = list(op[1])
-        elif op[0] == "drain":
-            drains.append(rows)
-            rows = {}
-    rec = np.asarray(recs, np.int64).reshape(-1, 4)
-    rec = rec[np.lexsort((rec[:, 1], rec[:, 0]))].astype(np.int32)
-    for sn in snaps:
-        for v in sn.values():
-            if isinstance(v, np.ndarray):
-                v.setflags(write=False)
-    rec.setflags(write=False)
-    return tuple(snaps), rec, tuple(drains)
+    """The oracle mirror with the create-time N a parameter (sets None: PAR + (N0,))."""
+    return U._oracle(_room, A, nbh, rooms, roe, sets, soe, ops, sel, PAR + (N0,))
 
 
-def _engine(room, A, N, nbh, E, par=PAR, epb=0, rng="philox", f64=False):
-    from ffm_amd.engine import Engine
-    m, s = _room(room)
-    return Engine(m, s.astype(np.float64) if f64 else s, n_envs=E, n_agents=N, agent_capacity=A,
-                  params=_params(par, nbh), rng=rng, seed=SEED, auto_reset=True, envs_per_block=epb)
+def _engine(room, A, N, nbh, E, par=PAR, **kw):
+    return U._engine(_room(room), A, nbh, E, create=par + (N,), **kw)
 
 
 def _pairs(rooms, nbh):
     return [_room(r) for r in rooms]
 
 
-def _snapshot(eng):
-    pos, cnt, dff = eng.get_state()
-    c = eng.counters()
-    return {"pos": pos, "cnt": cnt, "dff": dff, "eps": _episodes(eng), "agent_steps": c["agent_steps"],
-            "resets": c["resets"]}
-
-
-def _assert_same(got, want, what=""):
-    assert np.array_equal(got["cnt"], want["cnt"]), f"{what}: counts differ"
-    assert np.array_equal(got["eps"], want["eps"]), f"{what}: episodes differ"
-    for e in range(len(want["cnt"])):
-        n = want["cnt"][e]
-        assert np.array_equal(got["pos"][e, :n], want["pos"][e, :n]), f"{what}: positions differ (env {e})"
-    assert np.array_equal(got["dff"].view(np.uint32), want["dff"].view(np.uint32)), f"{what}: DFF bits differ"
-    assert got["agent_steps"] == want["agent_steps"], f"{what}: agent_steps"
-    assert got["resets"] == want["resets"], f"{what}: resets"
-
-
-def _assert_on(eng, n_rooms):
-    info = eng.launch_info()
-    assert info["kernel"] == "block" and info["env_rooms"] == n_rooms and info["step_shards"] == 1
-    return info
-
-
 def _room_eps(eps, roe, n_rooms):
     roe = np.asarray(roe)
     return [int(eps[roe == r].sum()) for r in range(n_rooms)]
-
-
-def _assert_coverage(eps, roe, n_rooms):
-    """Every room's own free list and F was placed from: an env of each ended an episode."""
-    roe = np.asarray(roe)
-    for r in range(n_rooms):
-        assert (eps[roe == r] > 0).any(), f"oracle: no env of room {r} ended an episode"
 
 
 def _roe(c):
@@ -438,7 +305,7 @@ def test_room_change_then_reset_envs(case):
     roe = tuple(e % R for e in range(E))
     roe2 = tuple((r + 1) % R if e % 2 == 0 else r for e, r in enumerate(roe))
     mask = tuple(1 if a != b else 0 for a, b in zip(roe, roe2))
-    ops = (("step", 25), ("snap",), ("roe", roe2), ("reset_envs", mask), ("step", 40), ("snap",))
+    ops = (("step", 25), ("snap",), ("rooms", roe2), ("reset_envs", mask), ("step", 40), ("snap",))
     want, _, _ = _oracle(c["A"], c["N"], nbh, c["rooms"], roe, None, None, ops)
     eng = _engine(c["rooms"][0], c["A"], c["N"], nbh, E)
     try:
