@@ -578,3 +578,166 @@ void ffo_core_step_philox_batch(const ffo_core_cfg* c, int64_t E, int32_t A_cap,
     free(fl);
     if (agent_steps) *agent_steps = total;
 }
+
+/* ======================================================================
+ * Searches for the Philox draws that no random run reaches
+ * (tools/find_rare_philox.py -> tests/golden/rare_philox.json).  Every draw is a
+ * pure function of (seed, t, global env, index, purpose), so the counters that
+ * land in a rare branch are found by enumeration: (t, env) over
+ * [t_lo, t_hi) x [env_lo, env_hi).  Each search stores up to `cap` rows of
+ * FFO_HIT_WORDS words, sorted by (t, env), and returns how many it found: the
+ * stored rows depend on the thread count only when that exceeds `cap`.
+ * ====================================================================== */
+static int cmp_hit(const void* a, const void* b) {
+    const uint32_t* x = (const uint32_t*)a;
+    const uint32_t* y = (const uint32_t*)b;
+    for (int i = 0; i < 2; i++)
+        if (x[i] != y[i]) return x[i] < y[i] ? -1 : 1;
+    return 0;
+}
+
+static void hit_store(uint32_t* hits, int64_t cap, int64_t* n, const uint32_t row[FFO_HIT_WORDS]) {
+#ifdef _OPENMP
+#pragma omp critical(ffo_hit)
+#endif
+    {
+        if (*n < cap) memcpy(hits + *n * FFO_HIT_WORDS, row, sizeof(uint32_t) * FFO_HIT_WORDS);
+        (*n)++;
+    }
+}
+
+static void hit_sort(uint32_t* hits, int64_t cap, int64_t n) {
+    qsort(hits, (size_t)(n < cap ? n : cap), sizeof(uint32_t) * FFO_HIT_WORDS, cmp_hit);
+}
+
+/* The engine's candidate threshold for a placement of N of F cells, restated
+ * (ffm_amd/csrc/core_common.h reset_threshold): floor((2N + 16) 2^32 / F), saturated;
+ * every key when N >= F.  A key k is a candidate when k <= threshold. */
+uint32_t ffo_reset_threshold(int32_t N, int32_t F) {
+    if (N >= F) return 0xFFFFFFFFu;
+    const uint64_t t = ((uint64_t)(2 * (int64_t)N + 16) << 32) / (uint64_t)F;
+    return t >= 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)t;
+}
+
+/* Friction of a target with m requesters owned by agent `owner` (draw_friction's Philox
+ * mode): the coin says "somebody moves" (z < 2^31), the owner's word w is rejected
+ * (low32(w m) < 2^32 mod m), the first word of the owner's friction stream is not, and the
+ * rank it gives differs from the rank (w m) >> 32 an unrejected w would have given.
+ * Row: t, env, unrejected rank, replacement rank, w, replacement word. */
+int64_t ffo_find_friction_reject(uint64_t seed, uint32_t m, uint32_t owner, uint32_t env_lo, uint32_t env_hi,
+                                 uint64_t t_lo, uint64_t t_hi, uint32_t* hits, int64_t cap, int nthreads) {
+    int64_t n = 0;
+    if (m < 2) return 0;
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    const uint32_t thr = (uint32_t)(-m) % m;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 65536) num_threads(nthreads > 0 ? nthreads : 1)
+#endif
+    for (int64_t tt = (int64_t)t_lo; tt < (int64_t)t_hi; tt++) {
+        const uint32_t t = (uint32_t)tt;
+        for (uint32_t env = env_lo; env < env_hi; env++) {
+            const uint32_t ctr[4] = {t, env, owner, (uint32_t)PUR_DECIDE << 28};
+            uint32_t b[4];
+            ffo_philox(ctr, key, b);
+            const uint64_t prod = (uint64_t)b[3] * m;
+            if (!((uint32_t)prod < thr)) continue;
+            if (b[2] >= 0x80000000u) continue;
+            pstream p;
+            ps_init(&p, seed, t, env, owner, PUR_FRICTION);
+            const uint32_t w1 = ps_next(&p);
+            const uint64_t prod1 = (uint64_t)w1 * m;
+            if ((uint32_t)prod1 < thr) continue;             /* a second rejection in a row: 2^-64 */
+            if ((prod1 >> 32) == (prod >> 32)) continue;
+            const uint32_t row[FFO_HIT_WORDS] = {t, env, (uint32_t)(prod >> 32), (uint32_t)(prod1 >> 32), b[3], w1};
+            hit_store(hits, cap, &n, row);
+        }
+    }
+    (void)nthreads;
+    hit_sort(hits, cap, n);
+    return n;
+}
+
+/* Placement over F free-list entries (reset_with_list's keys and (key, j) order): two equal
+ * keys at adjacent ranks r, r + 1 with r + 1 <= rmax.  Only the pairs at ranks 0 .. rmax
+ * matter, so a trial sorts the keys up to a bound that about rmax + 25 of them stay under,
+ * and all F of them when fewer than rmax + 1 did.
+ * Row: t, env, r, j at rank r, j at rank r + 1, the key. */
+int64_t ffo_find_reset_tie(uint64_t seed, int32_t F, int32_t rmax, uint32_t env_lo, uint32_t env_hi,
+                           uint64_t t_lo, uint64_t t_hi, uint32_t* hits, int64_t cap, int nthreads) {
+    int64_t n = 0;
+    if (F < 2 || rmax < 1) return 0;
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    const uint64_t b64 = ((uint64_t)(rmax + 25) << 32) / (uint64_t)F;
+    const uint32_t bound = b64 >= 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)b64;
+#ifdef _OPENMP
+#pragma omp parallel num_threads(nthreads > 0 ? nthreads : 1)
+#endif
+    {
+        uint64_t* all = (uint64_t*)malloc(sizeof(uint64_t) * (size_t)F);
+        uint64_t* low = (uint64_t*)malloc(sizeof(uint64_t) * (size_t)F);
+#ifdef _OPENMP
+#pragma omp for schedule(dynamic, 64)
+#endif
+        for (int64_t tt = (int64_t)t_lo; tt < (int64_t)t_hi; tt++) {
+            const uint32_t t = (uint32_t)tt;
+            for (uint32_t env = env_lo; env < env_hi; env++) {
+                int nl = 0;
+                for (int j = 0; j < F; j++) {
+                    const uint32_t ctr[4] = {t, env, (uint32_t)j, (uint32_t)PUR_RESET << 28};
+                    uint32_t o[4];
+                    ffo_philox(ctr, key, o);
+                    all[j] = ((uint64_t)o[0] << 32) | (uint64_t)j;
+                    if (o[0] <= bound) low[nl++] = all[j];
+                }
+                uint64_t* s = low;
+                int ns = nl;
+                if (nl < rmax + 1 && nl < F) { s = all; ns = F; }
+                qsort(s, (size_t)ns, sizeof(uint64_t), cmp_u64);
+                for (int r = 0; r + 1 <= rmax && r + 1 < ns; r++) {
+                    if ((s[r] >> 32) != (s[r + 1] >> 32)) continue;
+                    const uint32_t row[FFO_HIT_WORDS] = {t, env, (uint32_t)r, (uint32_t)s[r], (uint32_t)s[r + 1],
+                                                         (uint32_t)(s[r] >> 32)};
+                    hit_store(hits, cap, &n, row);
+                    break;
+                }
+            }
+        }
+        free(all);
+        free(low);
+    }
+    (void)nthreads;
+    hit_sort(hits, cap, n);
+    return n;
+}
+
+/* Placement of N of F cells whose threshold pass comes up short: fewer than N keys
+ * <= ffo_reset_threshold(N, F), so the engine retries with every key.  A trial stops at
+ * its N-th candidate.  Row: t, env, the candidates found, 0, 0, 0. */
+int64_t ffo_find_reset_short(uint64_t seed, int32_t F, int32_t N, uint32_t env_lo, uint32_t env_hi,
+                             uint64_t t_lo, uint64_t t_hi, uint32_t* hits, int64_t cap, int nthreads) {
+    int64_t n = 0;
+    if (N < 1 || N >= F) return 0;
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    const uint32_t T = ffo_reset_threshold(N, F);
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 4096) num_threads(nthreads > 0 ? nthreads : 1)
+#endif
+    for (int64_t tt = (int64_t)t_lo; tt < (int64_t)t_hi; tt++) {
+        const uint32_t t = (uint32_t)tt;
+        for (uint32_t env = env_lo; env < env_hi; env++) {
+            int c = 0;
+            for (int j = 0; j < F && c < N; j++) {
+                const uint32_t ctr[4] = {t, env, (uint32_t)j, (uint32_t)PUR_RESET << 28};
+                uint32_t o[4];
+                ffo_philox(ctr, key, o);
+                c += o[0] <= T ? 1 : 0;
+            }
+            if (c >= N) continue;
+            const uint32_t row[FFO_HIT_WORDS] = {t, env, (uint32_t)c, 0, 0, 0};
+            hit_store(hits, cap, &n, row);
+        }
+    }
+    (void)nthreads;
+    hit_sort(hits, cap, n);
+    return n;
+}

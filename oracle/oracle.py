@@ -104,6 +104,13 @@ def lib():
         L.ffo_reset_philox.argtypes = [C.POINTER(CoreCfg), C.c_int32, C.c_uint64, C.c_uint32,
                                        C.c_int64, P]
         L.ffo_reset_philox_list.argtypes = [P, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_int64, P]
+        L.ffo_reset_threshold.argtypes = [C.c_int32, C.c_int32]
+        L.ffo_reset_threshold.restype = C.c_uint32
+        for fn, a, b in ((L.ffo_find_friction_reject, C.c_uint32, C.c_uint32),
+                         (L.ffo_find_reset_tie, C.c_int32, C.c_int32),
+                         (L.ffo_find_reset_short, C.c_int32, C.c_int32)):
+            fn.argtypes = [C.c_uint64, a, b, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, P, C.c_int64, C.c_int]
+            fn.restype = C.c_int64
         _lib = L
     return _lib
 
@@ -211,6 +218,42 @@ def np_expf(x: np.ndarray, nthreads: int = 8) -> np.ndarray:
 def np_sumf(a: np.ndarray) -> np.float32:
     a = np.ascontiguousarray(a, dtype=np.float32)
     return np.float32(lib().ffo_np_sumf(_ptr(a), a.size))
+
+
+# -- searches for rare Philox draws (tools/find_rare_philox.py) -----------------
+HIT_WORDS = 6
+
+
+def reset_threshold(N: int, F: int) -> int:
+    """The engine's candidate threshold of a placement of N of F cells (a key <= it is kept)."""
+    return int(lib().ffo_reset_threshold(N, F))
+
+
+def _find(fn, seed, a, b, envs, ts, cap, nthreads) -> np.ndarray:
+    hits = np.zeros((cap, HIT_WORDS), np.uint32)
+    n = fn(seed, a, b, envs[0], envs[1], ts[0], ts[1], _ptr(hits), cap, nthreads)
+    if n > cap:
+        raise OverflowError(f"{n} hits for {cap} rows: search a smaller range")
+    return hits[:n]
+
+
+def find_friction_reject(seed, m, owner, envs, ts, cap=256, nthreads=8) -> np.ndarray:
+    """Rows (t, env, unrejected rank, replacement rank, w, replacement word), sorted by (t, env), over
+    envs = (lo, hi) and ts = (lo, hi): the friction draws of owner index `owner` with m requesters
+    whose word is rejected and whose replacement picks another rank."""
+    return _find(lib().ffo_find_friction_reject, seed, m, owner, envs, ts, cap, nthreads)
+
+
+def find_reset_tie(seed, F, rmax, envs, ts, cap=4096, nthreads=8) -> np.ndarray:
+    """Rows (t, env, r, j at rank r, j at rank r + 1, key): placements over F cells with two equal
+    keys at adjacent ranks r, r + 1 <= rmax."""
+    return _find(lib().ffo_find_reset_tie, seed, F, rmax, envs, ts, cap, nthreads)
+
+
+def find_reset_short(seed, F, N, envs, ts, cap=4096, nthreads=8) -> np.ndarray:
+    """Rows (t, env, count, 0, 0, 0): placements of N of F cells with count < N keys under
+    reset_threshold(N, F)."""
+    return _find(lib().ffo_find_reset_short, seed, F, N, envs, ts, cap, nthreads)
 
 
 def philox(ctr, key) -> np.ndarray:
