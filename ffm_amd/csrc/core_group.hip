@@ -59,11 +59,10 @@ struct GroupCarve {
 
 // The staged positions are dead once the agents are marked, so the kept-prefix
 // array reuses them; the placement keys are used only after the step loop (the
-// single-group form: after the step's stencil), so they reuse the grids and tiles.
-// FIT: the single-group form's own carve (kGroupFitCarve, an A/B build): grids, tiles, friction
-// words and the dummy word only.  That build takes the staged positions and the kept prefixes
-// from the lanes' registers, and the form never defers a placement.
-template <int G, bool FIT = false>
+// single-group form: after the step's stencil), so they reuse the grids and tiles.  Both forms
+// take this carve; the single-group form writes no kept prefixes and defers no placement, so of
+// kp it uses the staged positions only and pend stays unused.
+template <int G>
 __host__ __device__ inline GroupCarve group_carve(int PHW, int TS, int F) {
     GroupCarve c;
     size_t o = 0;
@@ -74,12 +73,6 @@ __host__ __device__ inline GroupCarve group_carve(int PHW, int TS, int F) {
     if (o < keys_end) o = keys_end;
     c.words = o; o += (size_t)G * 32 * 4;
     c.posst = o;
-    if (FIT) {
-        c.kp = c.pend = o;   // none of the three exists in this carve
-        c.dummy = o; o += 4;
-        c.per_wave = a16(o);
-        return c;
-    }
     // the compaction writes an entry for every lane of every agent chunk (idle lanes too: no
     // exec-mask branch), so the array spans whole chunks: (G * 32 + 63) / 64 * 64 + 1 entries
     c.kp = o;    o += a16((size_t)(((G * 32 + 63) / 64) * 64 + 1) * 2);
@@ -94,38 +87,28 @@ __host__ __device__ inline GroupCarve group_carve(int PHW, int TS, int F) {
 __host__ __device__ inline size_t group_shared_bytes(int PHW, int F) {
     return a16((size_t)PHW) + a16((size_t)PHW * 4) + a16((size_t)(F > 0 ? F : 1) * 2) + a16((size_t)PHW * 2);
 }
-// The single-group form's block-shared region under kGroupFitCarve: the SFF term alone.  The map and
-// the widened map are never read from LDS, and the free list, which only a placement reads, stays
-// in the image in global memory.
-__host__ __device__ inline size_t group_one_shared_bytes(int PHW) { return a16((size_t)PHW * 4); }
 
 // The room form's carve (per-env rooms, core_group_kernel<.., ROOM>).  No block-shared region: the
-// wave holds every env's own grid (stride room_layout().gs codes) and, in the FFM_GROUP_ROOM_SFF_LDS=1
-// build, its raw SFF (stride ss floats), so each is copied from the room table in whole 16-byte words.  The placement keys reuse the grids and
-// tiles (dead past the stencil) and are sized by F, the largest room's count.  The form is built on
-// the single-group form without a kept-prefix array (FFM_GROUP_FIT >= 1) and never defers a placement.
-struct GroupRoomCarve {
-    GroupCarve c;
-    size_t sff;
-};
-// SFFLDS false (the product build): no SFFs in LDS; decide reads them from the table.
-template <int G, bool SFFLDS = true>
-__host__ __device__ inline GroupRoomCarve group_room_carve(int PHW, int TS, int F) {
+// wave holds every env's own grid (stride room_layout().gs codes), copied from the room table in
+// whole 16-byte words; the SFFs stay in the table, where decide reads them.  The placement keys
+// reuse the grids and tiles (dead past the stencil) and are sized by F, the largest room's count.
+// The form is built on the single-group form: no kept-prefix array, and no placement is deferred.
+template <int G>
+__host__ __device__ inline GroupCarve group_room_carve(int PHW, int TS, int F) {
     const RoomLayout lay = room_layout(PHW, F);
-    GroupRoomCarve r;
+    GroupCarve c;
     size_t o = 0;
-    r.c.grid = o;  o += a16((size_t)G * lay.gs * 2);
-    r.c.tile = o;  o += a16((size_t)G * TS * 4);
-    r.c.keys = 0;
+    c.grid = o;  o += a16((size_t)G * lay.gs * 2);
+    c.tile = o;  o += a16((size_t)G * TS * 4);
+    c.keys = 0;
     const size_t keys_end = a16((size_t)(F > 0 ? F : 1) * 8);
     if (o < keys_end) o = keys_end;
-    r.sff = o;     o += SFFLDS ? a16((size_t)G * lay.ss * 4) : 0;
-    r.c.words = o; o += (size_t)G * 32 * 4;
-    r.c.posst = o; o += a16((size_t)G * 16 * 4);   // the group's position dwords (A <= 32)
-    r.c.kp = r.c.pend = o;                         // neither exists in this carve
-    r.c.dummy = o; o += 4;
-    r.c.per_wave = a16(o);
-    return r;
+    c.words = o; o += (size_t)G * 32 * 4;
+    c.posst = o; o += a16((size_t)G * 16 * 4);   // the group's position dwords (A <= 32)
+    c.kp = c.pend = o;                           // neither exists in this carve
+    c.dummy = o; o += 4;
+    c.per_wave = a16(o);
+    return c;
 }
 
 // The stage image (CoreStepArgs::stage): the block-shared region above byte for byte (pads zero),
@@ -201,10 +184,10 @@ __device__ __forceinline__ float lane_f32(float x, int l) {
 // control flow with all lanes active; csv is the chunk's cs word, wx / wy the decide draw.
 // PEP: psff is the raw SFF, and lane s < G of kSv / kDv holds env s's f32(-k_S) / f32(k_D); the
 // pending agent's env is wave-uniform here, so its two values are one readlane each.
-// SSE > 0 (the room form): psff holds one raw SFF per env of the group, SSE floats apart, and PHW is
-// the grids' stride.  SSE < 0 (the room form reading the SFF from the room table): psff is room 0's
-// SFF in the table, lane s < G of roomv holds env s's room index and rstride is the record stride in floats.
-template <int W, int PHW, int TS, bool PEP = false, int SSE = 0>
+// TABLE (the room form): PHW is the grids' stride and the SFF is read from the room table: psff is
+// room 0's SFF there, lane s < G of roomv holds env s's room index and rstride is the record stride
+// in floats.  Otherwise psff is the block's SFF in LDS.
+template <int W, int PHW, int TS, bool PEP = false, bool TABLE = false>
 __device__ __forceinline__ uint32_t group_exact_coop(unsigned long long pend, uint32_t slot, uint32_t csv, uint32_t wx,
                                                      uint32_t wy, const uint16_t* grid, const float* psff,
                                                      const float* tile, float kD, int lane, float kSv = 0.0f,
@@ -226,8 +209,8 @@ __device__ __forceinline__ uint32_t group_exact_coop(unsigned long long pend, ui
         const uint32_t g = grid[s * PHW + cell];
         // the valid candidates as a wave-uniform mask: free or exit neighbours, and the stay
         const unsigned vm = ((unsigned)__ballot(g == 0u || g == 3u) & ((1u << NB) - 1u)) | (1u << NB);   // :52-60
-        const float* sf = psff + (SSE > 0 ? s * SSE : 0);
-        if constexpr (SSE < 0) sf = psff + (size_t)__builtin_amdgcn_readlane(roomv, s) * (size_t)rstride;
+        const float* sf = psff;
+        if constexpr (TABLE) sf = psff + (size_t)__builtin_amdgcn_readlane(roomv, s) * (size_t)rstride;
         const float sa = PEP ? lane_f32(kSv, s) * sf[cell] : psff[cell];
         const float sb = (PEP ? lane_f32(kDv, s) : kD) * tile[s * TS + pp + dd0 + doff];
         const float sc = sa + sb;                                                      // :77
@@ -271,22 +254,8 @@ __device__ __forceinline__ uint32_t group_exact_coop(unsigned long long pend, ui
 
 }  // namespace
 
-#ifndef FFM_GROUP_PROBE_VALU
-#define FFM_GROUP_PROBE_VALU 0   // diagnostic builds only
-#endif
-#ifndef FFM_GROUP_PROBE_SALU
-#define FFM_GROUP_PROBE_SALU 0
-#endif
-#ifndef FFM_GROUP_PROBE_DUP
-#define FFM_GROUP_PROBE_DUP 0
-#endif
-
 #ifndef FFM_GROUP_ABLATE
 #define FFM_GROUP_ABLATE 0   // diagnostic builds only
-#endif
-
-#ifndef FFM_GROUP_TAIL
-#define FFM_GROUP_TAIL 1    // the stencil's partial last slot, one cell per lane
 #endif
 
 // Skeleton ladder (diagnostic builds only; results invalid, timing only; profiles/r06/c2/):
@@ -300,62 +269,17 @@ __device__ __forceinline__ uint32_t group_exact_coop(unsigned long long pend, ui
 #define FFM_GROUP_LADDER 4
 #endif
 
-// Where the next group's HBM loads are issued (diagnostic A/B): 0 before the stencil, 1 after
-// decide, 2 after mark, 3 right after the staging.
-#ifndef FFM_GROUP_PF
-#define FFM_GROUP_PF 0
-#endif
-
-// Waves that step fewer groups than the most loaded ones start late by s_sleep(N) (64 N
-// clocks): their phases leave the others' (diagnostic A/B; 0 = off).
-#ifndef FFM_GROUP_STAGGER
-#define FFM_GROUP_STAGGER 0
-#endif
-
-// The single-group form's LDS turns and arrays (profiles/lds_fit/).  1 is the product build; 0
-// (the form as it was), 2 and 3 are A/B builds: 2 and 3 measured slower at 32,768 envs.
-//   1: the compaction reads the kept prefixes from the lanes that hold them (no kp array)
-//   2: + the mark reads the positions from the lanes' registers (no posst array)
-//   3: + the form's own carve, 20,432 B per block at G = 4: eight blocks per CU
-#ifndef FFM_GROUP_FIT
-#define FFM_GROUP_FIT 1
-#endif
-constexpr bool kGroupFitCarve = FFM_GROUP_FIT >= 3;
-
-#ifndef FFM_GROUP_ONE_WAVES
-// The same for the single-group form (ONE).  Every instantiation stays below the 64 VGPRs of
-// eight waves per SIMD at 6 (tools/kernel_resources.py).  Asking for (8, 8) also cuts the SGPR
-// budget: FFM_GROUP_FIT=3 built that way spilled 10 - 99 scalars to VGPR lanes (SQ_INSTS_VALU
-// 671 -> 690 per wave in the headline kernel, profiles/lds_fit/).
-#define FFM_GROUP_ONE_WAVES 6
-#endif
-
 #ifndef FFM_GROUP_WAVES
 #define FFM_GROUP_WAVES 6   // minimum waves per SIMD asked of the register allocator (G = 4 needs 73 VGPRs; the grid holds 6 per SIMD)
 #endif
 
-// The Neumann kernels' exact decide as a wave-cooperative pass (group_exact_coop); 0 builds the
-// per-lane serial pass (A/B builds, profiles/decide_stencil/).
-#ifndef FFM_GROUP_COOP_EXACT
-#define FFM_GROUP_COOP_EXACT 1
+#ifndef FFM_GROUP_ONE_WAVES
+// The same for the single-group form (ONE).  Every instantiation stays below the 64 VGPRs of
+// eight waves per SIMD at 6 (tools/kernel_resources.py).  Asking for (8, 8) also cuts the SGPR
+// budget: a build that did spilled 10 - 99 scalars to VGPR lanes (SQ_INSTS_VALU 671 -> 690 per
+// wave in the headline kernel, profiles/lds_fit/).
+#define FFM_GROUP_ONE_WAVES 6
 #endif
-
-// PEP builds: how a lane takes the value of its agent's (its DFF slot's) env from the lanes that
-// hold the group's records.  1: one ds_bpermute per value; 0: G readlanes into wave-uniform
-// values and G - 1 selects (A/B builds; profiles/env_params_group/resources.txt has both).
-#ifndef FFM_GROUP_PEP_BPERMUTE
-#define FFM_GROUP_PEP_BPERMUTE 1
-#endif
-
-// The room form's SFFs (per-env rooms).  0, the product build: they stay in the room table and decide
-// reads the agent's env's room's SFF there, through L1 / L2 (a few rooms of 784 bytes each).  1 (an A/B
-// build) copies every env's raw SFF into the wave's LDS first: 3.1 KB more per wave at G = 4, 33.3 KB
-// per block and four blocks per CU instead of seven, and 30.85 against 23.07 us per step at 65,536
-// envs (slower at every size measured: profiles/env_rooms_group/ab.txt).
-#ifndef FFM_GROUP_ROOM_SFF_LDS
-#define FFM_GROUP_ROOM_SFF_LDS 0
-#endif
-constexpr bool kRoomSffLds = FFM_GROUP_ROOM_SFF_LDS != 0;
 
 #ifndef FFM_GROUP_G
 #define FFM_GROUP_G 4
@@ -385,10 +309,11 @@ constexpr int kGroupGSmall = FFM_GROUP_G_SMALL;   // envs per group when the lar
 // valid).  There is no block-shared region and no __syncthreads: the wave copies each env's grid codes
 // from its room's record of the table into its own LDS (group_room_carve; 16-byte loads spread over
 // the lanes, L2-resident), decide reads the agent's env's grid there and its room's raw SFF in the
-// table (FFM_GROUP_ROOM_SFF_LDS=1: from a copy in LDS), and a placement takes the env's room's free
-// list and F straight from the record.  Every index into a grid, an SFF
-// or a tile comes from a position (< H * W) or a host-validated free-list entry, none from a map
-// code: an env stepped in a room it was not placed in stays memory-safe (undefined for that env only).
+// table (through L1 / L2: a few rooms of 784 bytes each; copying them into the wave's LDS measured
+// slower at every size, profiles/env_rooms_group/ab.txt), and a placement takes the env's room's
+// free list and F straight from the record.  Every index into a grid, an SFF or a tile comes from
+// a position (< H * W) or a host-validated free-list entry, none from a map code: an env stepped in
+// a room it was not placed in stays memory-safe (undefined for that env only).
 template <int NB, int HT, int WT, int G, bool KD1, bool EPL, bool ONE, bool PEP = false, bool ROOM = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ONE ? FFM_GROUP_ONE_WAVES : FFM_GROUP_WAVES, 8)))
 void core_group_kernel(CoreStepArgs a) {
@@ -402,44 +327,31 @@ void core_group_kernel(CoreStepArgs a) {
     // a partial last slot of at most 16 float4s is stepped as one cell per lane instead
     // (G = 4 at 12x12: 144 float4s = 2 full slots + 64 cells), so its stencil keeps every
     // lane busy (Neumann only: the Moore stencil keeps the float4 form)
-    constexpr bool SCALAR_TAIL = NB == 4 && FFM_GROUP_TAIL && Q % 64 != 0 && (Q % 64) * 4 == 64;
+    constexpr bool SCALAR_TAIL = NB == 4 && Q % 64 != 0 && (Q % 64) * 4 == 64;
     constexpr int MAXC = (G * 32 + 63) / 64;   // agent chunks per group (A <= 32)
     constexpr int PWORDS = G * 16;             // position dwords per group (A <= 32)
     static_assert(G >= 1 && G <= 8 && HW % 4 == 0 && H + 1 < 128, "group geometry");
     static_assert(!PEP || !KD1, "the per-env form multiplies by every env's own k_D");
     static_assert(!ROOM || (PEP && ONE), "the room form takes every env's record and is built on the single-group form");
-    // the room form: grids and SFFs strided per env as in the room table (whole 16-byte words)
-    constexpr int GS = ROOM ? ((PHW + 7) & ~7) : PHW, SS = (PHW + 3) & ~3;
+    // the room form: grids strided per env as in the room table (whole 16-byte words)
+    constexpr int GS = ROOM ? ((PHW + 7) & ~7) : PHW;
     static_assert(MAXC * 64 >= G * 32 && PWORDS * 4 <= (MAXC * 64 + 1) * 2, "kp spans the chunks; posst fits in it");
-    // what the single-group form does without, by FFM_GROUP_FIT
-    constexpr bool NOKP = ONE && FFM_GROUP_FIT >= 1, NOPOS = ONE && FFM_GROUP_FIT >= 2, FITC = ONE && kGroupFitCarve;
-    static_assert(!NOPOS || PWORDS <= 64, "the group's positions are one dword per lane");
-    static_assert(!NOKP || MAXC <= 2, "the kept prefixes are read from the first or the last chunk");
-    static_assert(!ROOM || (NOKP && !NOPOS && !FITC), "the room form's carve: staged positions, no kept-prefix array");
+    // the single-group form has no kept-prefix array: its compaction reads the prefixes from the lanes
+    static_assert(!ONE || MAXC <= 2, "the kept prefixes are read from the first or the last chunk");
     const int A = a.A;
     const int lane = (int)(threadIdx.x & 63);
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 
-    size_t room_sff = 0;   // ROOM: the SFFs' offset in the wave's carve
     const GroupCarve cv = [&] {
-        if constexpr (ROOM) {
-            const GroupRoomCarve rc = group_room_carve<G, kRoomSffLds>(PHW, TS, a.F);
-            room_sff = rc.sff;
-            return rc.c;
-        } else
-            return group_carve<G, FITC>(PHW, TS, a.F);
+        if constexpr (ROOM) return group_room_carve<G>(PHW, TS, a.F);
+        else return group_carve<G>(PHW, TS, a.F);
     }();
     // block-shared (group_shared_bytes): the map and the widened map are in the image too, but
-    // the kernel reads only the SFF term and the free list from LDS.  FITC: the SFF term alone
-    // (group_one_shared_bytes), and the free list is read where it lies in the image.
+    // the kernel reads only the SFF term and the free list from LDS.  ROOM: neither is read.
     constexpr size_t kImgSff = ((size_t)PHW + 15) / 16 * 16, kImgFree = kImgSff + ((size_t)PHW * 4 + 15) / 16 * 16;
-    const float* psff = reinterpret_cast<const float*>(smem + (FITC ? 0 : kImgSff));
-    const uint16_t* pfree = FITC ? reinterpret_cast<const uint16_t*>(static_cast<const unsigned char*>(a.stage) + kImgFree)
-                                 : reinterpret_cast<const uint16_t*>(smem + kImgFree);
-    unsigned char* wbase = smem + (ROOM ? 0 : FITC ? group_one_shared_bytes(PHW) : group_shared_bytes(PHW, a.F)) +
-                           (size_t)wv * cv.per_wave;
-    // ROOM: psff and pfree above are not read; FFM_GROUP_ROOM_SFF_LDS=1: the group's SFFs, env s at sffw + s * SS
-    const float* const sffw = ROOM ? reinterpret_cast<const float*>(wbase + room_sff) : psff;
+    const float* psff = reinterpret_cast<const float*>(smem + kImgSff);
+    const uint16_t* pfree = reinterpret_cast<const uint16_t*>(smem + kImgFree);
+    unsigned char* wbase = smem + (ROOM ? 0 : group_shared_bytes(PHW, a.F)) + (size_t)wv * cv.per_wave;
     uint16_t* const grid = reinterpret_cast<uint16_t*>(wbase + cv.grid);
     float* const tile = reinterpret_cast<float*>(wbase + cv.tile);
     uint32_t* const words = reinterpret_cast<uint32_t*>(wbase + cv.words);
@@ -547,14 +459,9 @@ void core_group_kernel(CoreStepArgs a) {
         }
         if constexpr (PEP) load_rec(gg, st);
     };
-    // PEP: the value lane s holds (s < G, per lane: an agent's env, a DFF slot's env)
-    auto env_val = [&](float v, int s) {
-        if (FFM_GROUP_PEP_BPERMUTE)
-            return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(s * 4, __builtin_bit_cast(int, v)));
-        float r = lane_f32(v, 0);
-#pragma unroll
-        for (int q = 1; q < G; q++) r = s == q ? lane_f32(v, q) : r;
-        return r;
+    // PEP: the value lane s holds (s < G, per lane: an agent's env, a DFF slot's env), one ds_bpermute
+    auto env_val = [](float v, int s) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(s * 4, __builtin_bit_cast(int, v)));
     };
     // PEP: the placement of env e of this launch with its own N and threshold, read here: rare,
     // nothing of the step is live
@@ -571,12 +478,6 @@ void core_group_kernel(CoreStepArgs a) {
         else wave_reset_env<PW, true>(a, ebase + (uint32_t)e, keys, pfree, a.pos + e * A, lane);
     };
     constexpr int LAD = FFM_GROUP_LADDER;
-    constexpr int PF = FFM_GROUP_PF;
-    if (FFM_GROUP_STAGGER > 0) {
-        const int mine = g < ngroups ? (ngroups - 1 - g) / wstride + 1 : 0;
-        const int most = (ngroups - 1) / wstride + 1;
-        if (mine < most) __builtin_amdgcn_s_sleep(FFM_GROUP_STAGGER);
-    }
     GState cur;
     if (!ONE) load(g < ngroups ? g : -1, cur);
     else if (g < ngroups) load(g, cur);   // wave-uniform; cur is read under the same guard only
@@ -588,69 +489,55 @@ void core_group_kernel(CoreStepArgs a) {
             // group's base as the scalar offset: past the last env the load returns 0, room 0.
             roomv = (int)__builtin_amdgcn_raw_buffer_load_b32(pair_rsrc(a.room_of_env, (int)E * 4),
                                                                         lane < G ? lane * 4 : kOOB, g * G * 4, 0);
-            // Every env's grid codes and raw SFF from its room's record (the host checked every index
-            // and that room_stride is room_layout()'s): 16-byte word q of the G grids is word q % GQ of
-            // env q / GQ's, and lands at byte 16 q of the wave's grids, whose stride is the record's.
+            // Every env's grid codes from its room's record (the host checked every index and that
+            // room_stride is room_layout()'s): 16-byte word q of the G grids is word q % GQ of env
+            // q / GQ's, and lands at byte 16 q of the wave's grids, whose stride is the record's.
             const RoomLayout lay = room_layout(PHW, a.F);
-            constexpr int GQ = GS * 2 / 16, SQ = SS * 4 / 16;
-            static_assert((GS * 2) % 16 == 0 && (SS * 4) % 16 == 0, "whole 16-byte words per env");
-            // env s's index from the lane that holds it, taken with every lane active (s < G always)
-            auto room_of = [&](int s, int bit) {
-                const int r = __builtin_amdgcn_ds_bpermute(s * 4, roomv);
-                return (FFM_GROUP_ABLATE & bit) ? __builtin_amdgcn_readlane(roomv, 0) : r;   // diagnostic: env 0's room for all
-            };
+            constexpr int GQ = GS * 2 / 16;
+            static_assert((GS * 2) % 16 == 0, "whole 16-byte words per env");
 #pragma unroll
             for (int q0 = 0; q0 < G * GQ; q0 += 64) {
                 const int q = q0 + lane, s = min(q / GQ, G - 1);
-                const unsigned char* rec = a.rooms + (size_t)room_of(s, 4) * (size_t)a.room_stride;
+                // env s's index from the lane that holds it, taken with every lane active (s < G always)
+                // (diagnostic: env 0's room for all)
+                const int rb = __builtin_amdgcn_ds_bpermute(s * 4, roomv);
+                const int r = (FFM_GROUP_ABLATE & 4) ? __builtin_amdgcn_readlane(roomv, 0) : rb;
+                const unsigned char* rec = a.rooms + (size_t)r * (size_t)a.room_stride;
                 if (q < G * GQ)
                     reinterpret_cast<uint4*>(grid)[q] = reinterpret_cast<const uint4*>(rec + lay.grid)[q - s * GQ];
-            }
-#pragma unroll
-            for (int q0 = 0; q0 < (kRoomSffLds ? G * SQ : 0); q0 += 64) {
-                const int q = q0 + lane, s = min(q / SQ, G - 1);
-                const unsigned char* rec = a.rooms + (size_t)room_of(s, 2) * (size_t)a.room_stride;
-                if (q < G * SQ)
-                    reinterpret_cast<uint4*>(wbase + room_sff)[q] = reinterpret_cast<const uint4*>(rec + lay.sff)[q - s * SQ];
             }
             // the tiles' halos, as below
             if ((geo >> 24) != 255u) reinterpret_cast<float4*>(tile)[geo >> 24] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        // the wave's own grids, SFFs and halos before its mark and decide read them: no block-wide barrier
+        // the wave's own grids and halos before its mark and decide read them: no block-wide barrier
         if (LAD >= 1) wave_sync();
     } else if (LAD >= 1) {
-    // Block-shared region: the image's first sq4 float4s, one 16-byte load and LDS store per
-    // thread (the host checks sq4 <= 256).  The map, f32(-k_S) * SFF, the free list and the
-    // widened map are engine constants: nothing is recomputed per launch.
-    // FITC: only the SFF term, PHW * 4 bytes of the image from kImgSff on.
-    static_assert((PHW * 4) % 16 == 0 && PHW * 4 / 16 <= 256, "16-B copies of the SFF term, one per thread");
-    if (FITC) {
-        if ((int)threadIdx.x < PHW * 4 / 16)
+        // Block-shared region: the image's first sq4 float4s, one 16-byte load and LDS store per
+        // thread (the host checks sq4 <= 256).  The map, f32(-k_S) * SFF, the free list and the
+        // widened map are engine constants: nothing is recomputed per launch.
+        if ((int)threadIdx.x < sq4)
             reinterpret_cast<uint4*>(smem)[threadIdx.x] = __builtin_bit_cast(
-                uint4, __builtin_amdgcn_raw_buffer_load_b128(rS, (int)threadIdx.x * 16, (int)kImgSff, 0));
-    } else if ((int)threadIdx.x < sq4)
-        reinterpret_cast<uint4*>(smem)[threadIdx.x] = __builtin_bit_cast(
-            uint4, __builtin_amdgcn_raw_buffer_load_b128(rS, (int)threadIdx.x * 16, 0, 0));
-    // Every env's grid starts as the map: the widened map straight from the image (8 bytes per
-    // lane, G LDS stores), so the wave's own state does not wait for the block's.
-    static_assert((PHW * 2) % 8 == 0 && PHW * 2 / 8 <= 64, "8-B grid copies, one per lane");
-    if (lane < PHW * 2 / 8) {
-        const int pm16 = (int)(a16((size_t)PHW) + a16((size_t)PHW * 4) + a16((size_t)(a.F > 0 ? a.F : 1) * 2));
-        const auto mw = __builtin_amdgcn_raw_buffer_load_b64(rS, lane * 8, pm16, 0);
+                uint4, __builtin_amdgcn_raw_buffer_load_b128(rS, (int)threadIdx.x * 16, 0, 0));
+        // Every env's grid starts as the map: the widened map straight from the image (8 bytes per
+        // lane, G LDS stores), so the wave's own state does not wait for the block's.
+        static_assert((PHW * 2) % 8 == 0 && PHW * 2 / 8 <= 64, "8-B grid copies, one per lane");
+        if (lane < PHW * 2 / 8) {
+            const int pm16 = (int)(a16((size_t)PHW) + a16((size_t)PHW * 4) + a16((size_t)(a.F > 0 ? a.F : 1) * 2));
+            const auto mw = __builtin_amdgcn_raw_buffer_load_b64(rS, lane * 8, pm16, 0);
 #pragma unroll
-        for (int s = 0; s < G; s++)
-            *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(grid) + s * (PHW * 2) + lane * 8) =
-                __builtin_bit_cast(uint2, mw);
-    }
-    // Only the tiles' halos are cleared (the zero rows above and below the map with the 4 floats
-    // before and after them, G * 8 float4s: one store).  The interior needs no clear: every
-    // iteration stages all NS slots of its group before anything reads the tile, a partial
-    // group's loads return the arrays' zeroed padding, and loads past the last group go through
-    // the empty resource and return zero.  Nothing ever writes the halo.
-    if ((geo >> 24) != 255u) reinterpret_cast<float4*>(tile)[geo >> 24] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!ONE && lane < kGroupPendWords) pend[lane] = 0u;
-    // the block-shared region is first read by decide (the SFF term) and by the placement tail
-    __syncthreads();
+            for (int s = 0; s < G; s++)
+                *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(grid) + s * (PHW * 2) + lane * 8) =
+                    __builtin_bit_cast(uint2, mw);
+        }
+        // Only the tiles' halos are cleared (the zero rows above and below the map with the 4 floats
+        // before and after them, G * 8 float4s: one store).  The interior needs no clear: every
+        // iteration stages all NS slots of its group before anything reads the tile, a partial
+        // group's loads return the arrays' zeroed padding, and loads past the last group go through
+        // the empty resource and return zero.  Nothing ever writes the halo.
+        if ((geo >> 24) != 255u) reinterpret_cast<float4*>(tile)[geo >> 24] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!ONE && lane < kGroupPendWords) pend[lane] = 0u;
+        // the block-shared region is first read by decide (the SFF term) and by the placement tail
+        __syncthreads();
     }
 
     unsigned c_steps = 0, c_exits = 0, c_resets = 0;
@@ -688,283 +575,250 @@ void core_group_kernel(CoreStepArgs a) {
 #pragma unroll
         for (int k = 0; k < NS; k++)
             if (k < NSF || toff[k] >= 0) *reinterpret_cast<float4*>(tile + toff[k]) = cur.d[k];
-        if (!ONE && PF == 3) load(gn, nxt);
         unsigned long long rsm = 0ull;   // envs re-placed at the end of this step
         if (LAD == 2) wave_sync();       // ladder rung 2: the staged tile before the stencil reads it
         if (LAD >= 3) {
-        // NOPOS: the positions stay in p0 of lanes 0..PWORDS-1; the mark reads them across lanes
-        if (!NOPOS && lane < PWORDS) posst32[lane] = cur.p0;
-        if (!NOPOS && PWORDS > 64 && 64 + lane < PWORDS) posst32[64 + lane] = cur.p1;
-        int S[G + 1];   // exclusive prefix of the counts (wave-uniform)
-        S[0] = 0;
+            if (lane < PWORDS) posst32[lane] = cur.p0;
+            if (PWORDS > 64 && 64 + lane < PWORDS) posst32[64 + lane] = cur.p1;
+            int S[G + 1];   // exclusive prefix of the counts (wave-uniform)
+            S[0] = 0;
 #pragma unroll
-        for (int s = 0; s < G; s++) S[s + 1] = S[s] + __builtin_amdgcn_readlane(cur.c, s);
-        const int T = S[G];
-        c_steps += (unsigned)T;
-        // posst before the mark reads it.  NOPOS: nothing in LDS to order here; the grids were
-        // initialised behind the prologue's barrier, and the staged tile is first read by decide,
-        // behind the mark's wave_sync
-        if (!NOPOS) wave_sync();
+            for (int s = 0; s < G; s++) S[s + 1] = S[s] + __builtin_amdgcn_readlane(cur.c, s);
+            const int T = S[G];
+            c_steps += (unsigned)T;
+            wave_sync();   // posst before the mark reads it
 
-        // ---- packed agents: cell and occupancy mark ------------------------------------
-        uint32_t cs[MAXC], cr[MAXC];
+            // ---- packed agents: cell and occupancy mark ------------------------------------
+            uint32_t cs[MAXC], cr[MAXC];
 #pragma unroll
-        for (int c = 0; c < MAXC; c++) {
-            cs[c] = (uint32_t)(PW + 1) | (1u << 25);   // idle: an in-bounds cell
-            cr[c] = 15u;
-            if (c * 64 < T) {
-                const int j = c * 64 + lane;
-                int s = 0, st = 0;
+            for (int c = 0; c < MAXC; c++) {
+                cs[c] = (uint32_t)(PW + 1) | (1u << 25);   // idle: an in-bounds cell
+                cr[c] = 15u;
+                if (c * 64 < T) {
+                    const int j = c * 64 + lane;
+                    int s = 0, st = 0;
 #pragma unroll
-                for (int q = 1; q < G; q++) {
-                    const bool ge = j >= S[q];
-                    s += ge ? 1 : 0;
-                    st = ge ? S[q] : st;
+                    for (int q = 1; q < G; q++) {
+                        const bool ge = j >= S[q];
+                        s += ge ? 1 : 0;
+                        st = ge ? S[q] : st;
+                    }
+                    const bool live = j < T;
+                    const int al = live ? j - st : 0;
+                    const uint32_t p = posst[live ? s * A + al : 0];
+                    const int x = (int)__umulhi(p, mW);
+                    const int y = (int)p - x * W;
+                    const int pp = live ? (x + 1) * PW + y + 1 : PW + 1;
+                    grid[live ? s * GS + pp : kDummy16] =
+                        (uint16_t)(DirCodes::kAgent | (uint32_t)al | (DirCodes::kNoDir << 8));
+                    cs[c] = (uint32_t)pp | ((uint32_t)al << 16) | ((uint32_t)s << 21) | ((live ? 1u : 0u) << 24) |
+                            ((uint32_t)(live ? x + 1 : 1) << 25);
                 }
-                const bool live = j < T;
-                const int al = live ? j - st : 0;
-                // NOPOS: half idx & 1 of position dword idx >> 1, held by that lane (idx < G * A <=
-                // 128); all lanes are active here (T is wave-uniform), as the permute needs
-                const int idx = live ? s * A + al : 0;
-                uint32_t p;
-                if (NOPOS) {
-                    const uint32_t pw = (uint32_t)__builtin_amdgcn_ds_bpermute((idx >> 1) * 4, (int)cur.p0);
-                    p = (idx & 1) ? pw >> 16 : pw & 0xFFFFu;
-                } else
-                    p = posst[idx];
-                const int x = (int)__umulhi(p, mW);
-                const int y = (int)p - x * W;
-                const int pp = live ? (x + 1) * PW + y + 1 : PW + 1;
-                grid[live ? s * GS + pp : kDummy16] = (uint16_t)(DirCodes::kAgent | (uint32_t)al | (DirCodes::kNoDir << 8));
-                cs[c] = (uint32_t)pp | ((uint32_t)al << 16) | ((uint32_t)s << 21) | ((live ? 1u : 0u) << 24) |
-                        ((uint32_t)(live ? x + 1 : 1) << 25);
             }
-        }
-        wave_sync();
+            wave_sync();
 
-        if (!ONE && PF == 2) load(gn, nxt);
-        // ---- decide (model/ffm_core.py:40-88) -------------------------------------------
+            // ---- decide (model/ffm_core.py:40-88) -------------------------------------------
 #pragma unroll
-        for (int c = 0; c < MAXC; c++) {
-            if (LAD == 3) cr[c] = DirCodes::kNoDir;   // ladder: every agent stays, no request
-            if (LAD >= 4 && c * 64 < T) {
-                const uint32_t v = cs[c];
-                const int pp = cs_pp(v), al = cs_al(v), s = cs_s(v);
-                const bool live = cs_live(v);
-                const uint32_t genv = ebase + (uint32_t)e0 + (uint32_t)s;
-                const uint4 pb = philox(make_uint4(a.t, genv, (uint32_t)al, kPurDecide << 28), a.key0, a.key1);
-                words[live ? s * 32 + al : kDummy32] = pb.w;   // the friction draw, if this agent owns a contested target
-                const uint16_t* gk = grid + s * GS;
-                const float* dk = tile + s * TS;
-                const int dd0 = 3 - 2 * cs_xp1(v);
-                bool to_exit = false;
-                // ROOM: the agent's env's own SFF (idle lanes: env 0's)
-                const float* sk = psff;
-                if constexpr (ROOM) {
-                    if (kRoomSffLds) sk = sffw + s * SS;
-                    else {   // the agent's env's room's SFF where it lies in the table (every lane is active here)
+            for (int c = 0; c < MAXC; c++) {
+                if (LAD == 3) cr[c] = DirCodes::kNoDir;   // ladder: every agent stays, no request
+                if (LAD >= 4 && c * 64 < T) {
+                    const uint32_t v = cs[c];
+                    const int pp = cs_pp(v), al = cs_al(v), s = cs_s(v);
+                    const bool live = cs_live(v);
+                    const uint32_t genv = ebase + (uint32_t)e0 + (uint32_t)s;
+                    const uint4 pb = philox(make_uint4(a.t, genv, (uint32_t)al, kPurDecide << 28), a.key0, a.key1);
+                    // the friction draw, if this agent owns a contested target
+                    words[live ? s * 32 + al : kDummy32] = pb.w;
+                    const uint16_t* gk = grid + s * GS;
+                    const float* dk = tile + s * TS;
+                    const int dd0 = 3 - 2 * cs_xp1(v);
+                    bool to_exit = false;
+                    // ROOM: the agent's env's room's SFF where it lies in the table (idle lanes: env 0's;
+                    // every lane is active here)
+                    const float* sk = psff;
+                    if constexpr (ROOM) {
                         const int r = (FFM_GROUP_ABLATE & 2) ? __builtin_amdgcn_readlane(roomv, 0)
                                                              : __builtin_amdgcn_ds_bpermute(s * 4, roomv);
                         sk = reinterpret_cast<const float*>(a.rooms + (size_t)r * (size_t)a.room_stride +
                                                             room_layout(PHW, a.F).sff);
                     }
-                }
-                // PEP: the agent's env's k_S / k_D (idle lanes: env 0's), on the raw SFF
-                float kSe = a.kS32, kDe = a.kD32;
-                if constexpr (PEP) {
-                    kSe = env_val(cur.pr.x, s);
-                    kDe = env_val(cur.pr.y, s);
-                }
-                uint32_t slot = PEP ? lane_decide<NB, false, false>(pp, PW, gk, sk, dk, dd0, kSe, kDe, pb.x, to_exit)
-                                    : lane_decide<NB, true, KD1>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32, pb.x, to_exit);
-                slot = live ? slot : kNoReq;
-                // u near a cdf boundary: the exact NumPy arithmetic decides
-                if (NB == 4 && FFM_GROUP_COOP_EXACT) {
-                    const unsigned long long pm = __ballot(slot == kPending);
-                    if (pm)   // wave-uniform, rare
-                        slot = !PEP ? group_exact_coop<W, PHW, TS>(pm, slot, v, pb.x, pb.y, grid, psff, tile, a.kD32, lane)
-                               : ROOM && !kRoomSffLds
-                                   ? group_exact_coop<W, GS, TS, true, -1>(
-                                         pm, slot, v, pb.x, pb.y, grid,
-                                         reinterpret_cast<const float*>(a.rooms + room_layout(PHW, a.F).sff), tile, 0.0f,
-                                         lane, cur.pr.x, cur.pr.y, roomv, a.room_stride / 4)
-                                   : group_exact_coop<W, GS, TS, true, ROOM ? SS : 0>(pm, slot, v, pb.x, pb.y, grid, sffw, tile,
-                                                                                      0.0f, lane, cur.pr.x, cur.pr.y);
-                } else if (slot == kPending)
-                    slot = NB == 4 ? lane_decide_exact<NB, !PEP>(pp, PW, gk, sk, dk, dd0, kSe, kDe, u53(pb.x, pb.y))
-                                   : lane_decide_exact_arr<NB, !PEP>(pp, PW, gk, sk, dk, dd0, kSe, kDe,
-                                                                     u53(pb.x, pb.y));
-                const uint32_t sd = slot <= (uint32_t)NB ? slot : DirCodes::kNoDir;
-                grid[live ? s * GS + pp : kDummy16] =
-                    (uint16_t)(DirCodes::kAgent | (uint32_t)al | (sd << 8) | ((pb.z >> 31) << 12));
-                cr[c] = sd | ((to_exit ? 1u : 0u) << 4);
-#if FFM_GROUP_PROBE_DUP
-                if (c == MAXC - 1) {   // diagnostic (timing only): the last chunk's draw and decide again
-                    uint32_t salt;
-                    asm volatile("v_mov_b32 %0, 0" : "=v"(salt));
-                    const uint4 pb2 = philox(make_uint4(a.t, genv, (uint32_t)al + salt, kPurDecide << 28), a.key0,
-                                             a.key1);
-                    bool te2 = false;
-                    const uint32_t slot2 =
-                        lane_decide<NB, true, KD1>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32, pb2.x, te2);
-                    asm volatile("" ::"v"(slot2), "v"(pb2.w), "v"(te2 ? 1u : 0u));
-                }
-#endif
-            }
-        }
-        wave_sync();
-
-        if (!ONE && PF == 1) load(gn, nxt);
-        // ---- resolve (model/ffm_core.py:90-98), by each requester ------------------------
-        unsigned long long km[MAXC];
-        int kept = 0;
-#pragma unroll
-        for (int c = 0; c < MAXC; c++) {
-            km[c] = 0ull;
-            if (c * 64 < T) {
-                const uint32_t v = cs[c];
-                const int pp = cs_pp(v), al = cs_al(v), s = cs_s(v);
-                const bool live = cs_live(v);
-                const uint32_t sd = cr[c] & 15u;
-                const bool to_exit = (cr[c] & 16u) != 0u;
-                const uint32_t slot = sd == DirCodes::kNoDir ? (uint32_t)kNoReq : sd;
-                const uint16_t* gk = grid + s * GS;
-                const int r = (int)slot_cell_k<NB, PW>(slot, pp);
-                const bool req = slot <= (uint32_t)NB;
-                const bool moving = req && r != pp;
-                bool granted = req && !moving;   // a stay is always granted
-                if (LAD >= 4) {
-                    const int rt = moving ? r : pp;
-                    int m = 0, k = 0, o = 0x7F;
-                    uint32_t zo = 0u;
-#pragma unroll
-                    for (int d = 0; d < NB; d++) {
-                        const uint32_t cc = gk[rt - nb_dx<NB>(d) * PW - nb_dy<NB>(d)];
-                        const bool is = (cc & DirCodes::kAgent) != 0u && ((cc >> 8) & 0xFu) == (uint32_t)d;
-                        const int who = (int)(cc & DirCodes::kIdx);
-                        m += is ? 1 : 0;
-                        k += (is && who < al) ? 1 : 0;
-                        const bool lower = is && who < o;
-                        zo = lower ? (cc >> 12) & 1u : zo;
-                        o = lower ? who : o;
+                    // PEP: the agent's env's k_S / k_D (idle lanes: env 0's), on the raw SFF
+                    float kSe = a.kS32, kDe = a.kD32;
+                    if constexpr (PEP) {
+                        kSe = env_val(cur.pr.x, s);
+                        kDe = env_val(cur.pr.y, s);
                     }
-                    granted = moving ? m == 1 : granted;   // an uncontested move is granted
-                    if (moving && m > 1) {
-                        const uint32_t w = words[s * 32 + o];
-                        const uint32_t genv = ebase + (uint32_t)e0 + (uint32_t)s;
-                        const int kk = philox_friction(zo << 31, w, (uint32_t)m, a.key0, a.key1, a.t, genv,
-                                                       (uint32_t)o);
-                        granted = kk == k;   // :95-96
-                    }
+                    uint32_t slot =
+                        PEP ? lane_decide<NB, false, false>(pp, PW, gk, sk, dk, dd0, kSe, kDe, pb.x, to_exit)
+                            : lane_decide<NB, true, KD1>(pp, PW, gk, psff, dk, dd0, a.kS32, a.kD32, pb.x, to_exit);
+                    slot = live ? slot : kNoReq;
+                    // u near a cdf boundary: the exact NumPy arithmetic decides
+                    if (NB == 4) {   // Neumann: one pending agent at a time across the wave
+                        const unsigned long long pm = __ballot(slot == kPending);
+                        if (pm) {   // wave-uniform, rare
+                            if constexpr (ROOM)
+                                slot = group_exact_coop<W, GS, TS, true, true>(
+                                    pm, slot, v, pb.x, pb.y, grid,
+                                    reinterpret_cast<const float*>(a.rooms + room_layout(PHW, a.F).sff), tile, 0.0f, lane,
+                                    cur.pr.x, cur.pr.y, roomv, a.room_stride / 4);
+                            else if constexpr (PEP)
+                                slot = group_exact_coop<W, PHW, TS, true>(pm, slot, v, pb.x, pb.y, grid, psff, tile, 0.0f,
+                                                                          lane, cur.pr.x, cur.pr.y);
+                            else
+                                slot = group_exact_coop<W, PHW, TS>(pm, slot, v, pb.x, pb.y, grid, psff, tile, a.kD32, lane);
+                        }
+                    } else if (slot == kPending)   // Moore: per lane
+                        slot = lane_decide_exact_arr<NB, !PEP>(pp, PW, gk, sk, dk, dd0, kSe, kDe, u53(pb.x, pb.y));
+                    const uint32_t sd = slot <= (uint32_t)NB ? slot : DirCodes::kNoDir;
+                    grid[live ? s * GS + pp : kDummy16] =
+                        (uint16_t)(DirCodes::kAgent | (uint32_t)al | (sd << 8) | ((pb.z >> 31) << 12));
+                    cr[c] = sd | ((to_exit ? 1u : 0u) << 4);
                 }
-                // :91-98 -- the mover's source cell gains 1 (one agent per cell: no collisions)
-                if (granted)
-                    __hip_atomic_fetch_add(tile + s * TS + pp + 3 - 2 * cs_xp1(v), 1.0f, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_WAVEFRONT);
-                const int np = granted ? r : pp;
-                const bool keep = live && !(granted && to_exit);
-                km[c] = __ballot(keep);
-                const int kpv = kept + lanes_below(km[c]);
-                kept += __popcll(km[c]);
-                cr[c] = (uint32_t)np | ((keep ? 1u : 0u) << 16) | ((uint32_t)kpv << 17);
             }
-        }
+            wave_sync();
 
-        // ---- exits: order-preserving compaction (model/ffm_core.py:100-102) ---------------
+            // ---- resolve (model/ffm_core.py:90-98), by each requester ------------------------
+            unsigned long long km[MAXC];
+            int kept = 0;
 #pragma unroll
-        for (int c = 0; c < MAXC; c++) {
-            if (c * 64 < T) {
-                const uint32_t v = cs[c];
-                if (!NOKP) kp[c * 64 + lane] = (uint16_t)(cr[c] >> 17);   // idle lanes' entries are never read
-                grid[cs_live(v) ? cs_s(v) * GS + cs_pp(v) : kDummy16] = 0;   // unmark: agents stand on free cells
+            for (int c = 0; c < MAXC; c++) {
+                km[c] = 0ull;
+                if (c * 64 < T) {
+                    const uint32_t v = cs[c];
+                    const int pp = cs_pp(v), al = cs_al(v), s = cs_s(v);
+                    const bool live = cs_live(v);
+                    const uint32_t sd = cr[c] & 15u;
+                    const bool to_exit = (cr[c] & 16u) != 0u;
+                    const uint32_t slot = sd == DirCodes::kNoDir ? (uint32_t)kNoReq : sd;
+                    const uint16_t* gk = grid + s * GS;
+                    const int r = (int)slot_cell_k<NB, PW>(slot, pp);
+                    const bool req = slot <= (uint32_t)NB;
+                    const bool moving = req && r != pp;
+                    bool granted = req && !moving;   // a stay is always granted
+                    if (LAD >= 4) {
+                        const int rt = moving ? r : pp;
+                        int m = 0, k = 0, o = 0x7F;
+                        uint32_t zo = 0u;
+#pragma unroll
+                        for (int d = 0; d < NB; d++) {
+                            const uint32_t cc = gk[rt - nb_dx<NB>(d) * PW - nb_dy<NB>(d)];
+                            const bool is = (cc & DirCodes::kAgent) != 0u && ((cc >> 8) & 0xFu) == (uint32_t)d;
+                            const int who = (int)(cc & DirCodes::kIdx);
+                            m += is ? 1 : 0;
+                            k += (is && who < al) ? 1 : 0;
+                            const bool lower = is && who < o;
+                            zo = lower ? (cc >> 12) & 1u : zo;
+                            o = lower ? who : o;
+                        }
+                        granted = moving ? m == 1 : granted;   // an uncontested move is granted
+                        if (moving && m > 1) {
+                            const uint32_t w = words[s * 32 + o];
+                            const uint32_t genv = ebase + (uint32_t)e0 + (uint32_t)s;
+                            const int kk = philox_friction(zo << 31, w, (uint32_t)m, a.key0, a.key1, a.t, genv,
+                                                           (uint32_t)o);
+                            granted = kk == k;   // :95-96
+                        }
+                    }
+                    // :91-98 -- the mover's source cell gains 1 (one agent per cell: no collisions)
+                    if (granted)
+                        __hip_atomic_fetch_add(tile + s * TS + pp + 3 - 2 * cs_xp1(v), 1.0f, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_WAVEFRONT);
+                    const int np = granted ? r : pp;
+                    const bool keep = live && !(granted && to_exit);
+                    km[c] = __ballot(keep);
+                    const int kpv = kept + lanes_below(km[c]);
+                    kept += __popcll(km[c]);
+                    cr[c] = (uint32_t)np | ((keep ? 1u : 0u) << 16) | ((uint32_t)kpv << 17);
+                }
             }
-        }
-        if (!NOKP && lane == 0) kp[T] = (uint16_t)kept;
-        c_exits += (unsigned)(T - kept);
-        // NOKP: the kept prefix at an env's start is the popcount of the resolve ballots below it
-        // (the bits of idle lanes and of a chunk that did not run are zero, so base[G] = kept):
-        // wave-uniform, and no LDS turn before the position stores
-        int base[G + 1];
-        base[0] = 0;
-        base[G] = kept;
+
+            // ---- exits: order-preserving compaction (model/ffm_core.py:100-102) ---------------
 #pragma unroll
-        for (int s = 1; s < G; s++) {
-            base[s] = 0;
-            if (NOKP) {
-                // the lane at packed index S[s] holds that popcount as its own kept prefix (a live
-                // lane of a chunk that ran, whenever S[s] < T; past T every later env is empty)
-                int b = __builtin_amdgcn_readlane((int)(cr[0] >> 17), S[s] & 63);
-                if (MAXC > 1) b = S[s] < 64 ? b : __builtin_amdgcn_readlane((int)(cr[MAXC - 1] >> 17), S[s] & 63);
-                base[s] = S[s] < T ? b : kept;
+            for (int c = 0; c < MAXC; c++) {
+                if (c * 64 < T) {
+                    const uint32_t v = cs[c];
+                    if (!ONE) kp[c * 64 + lane] = (uint16_t)(cr[c] >> 17);   // idle lanes' entries are never read
+                    grid[cs_live(v) ? cs_s(v) * GS + cs_pp(v) : kDummy16] = 0;   // unmark: agents stand on free cells
+                }
             }
-        }
-        if (!NOKP) wave_sync();
+            if (!ONE && lane == 0) kp[T] = (uint16_t)kept;
+            c_exits += (unsigned)(T - kept);
+            // ONE: the kept prefix at an env's start is the popcount of the resolve ballots below it
+            // (the bits of idle lanes and of a chunk that did not run are zero, so base[G] = kept):
+            // wave-uniform, and no LDS turn before the position stores
+            int base[G + 1];
+            base[0] = 0;
+            base[G] = kept;
 #pragma unroll
-        for (int c = 0; c < MAXC; c++) {
-            if (c * 64 < T) {
-                const uint32_t v = cs[c], w = cr[c];
-                const int j = c * 64 + lane;
-                const int s = cs_s(v);
-                const bool keep = ((w >> 16) & 1u) != 0u;
-                const int start = j - cs_al(v);
-                int bs = base[0];
-#pragma unroll
-                for (int q = 1; q < G; q++) bs = s == q ? base[q] : bs;
-                const int newidx = (int)(w >> 17) - (NOKP ? bs : (int)kp[cs_live(v) ? start : 0]);
-                __builtin_amdgcn_raw_buffer_store_b16((uint16_t)unpad((int)(w & 0xFFFFu), PW), rP,
-                                                      keep ? (s * A + newidx) * 2 : kOOB, e0 * A * 2, 0);
+            for (int s = 1; s < G; s++) {
+                base[s] = 0;
+                if (ONE) {
+                    // the lane at packed index S[s] holds that popcount as its own kept prefix (a live
+                    // lane of a chunk that ran, whenever S[s] < T; past T every later env is empty)
+                    int b = __builtin_amdgcn_readlane((int)(cr[0] >> 17), S[s] & 63);
+                    if (MAXC > 1)
+                        b = S[s] < 64 ? b : __builtin_amdgcn_readlane((int)(cr[MAXC - 1] >> 17), S[s] & 63);
+                    base[s] = S[s] < T ? b : kept;
+                }
             }
-        }
-        int Sl = T, Sh = T;   // lane s < G: [S[s], S[s+1])
-        int nk = 0;           // lane s < G: the env's new count
-        bool had;             // ... and whether it had agents
-        if (NOKP) {
+            if (!ONE) wave_sync();   // kp before the position stores read it
 #pragma unroll
-            for (int s = 0; s < G; s++) nk = lane == s ? base[s + 1] - base[s] : nk;
-            had = cur.c > 0;
-        } else {
+            for (int c = 0; c < MAXC; c++) {
+                if (c * 64 < T) {
+                    const uint32_t v = cs[c], w = cr[c];
+                    const int j = c * 64 + lane;
+                    const int s = cs_s(v);
+                    const bool keep = ((w >> 16) & 1u) != 0u;
+                    const int start = j - cs_al(v);
+                    int bs = base[0];
 #pragma unroll
-            for (int s = 0; s < G; s++) {
-                Sl = lane == s ? S[s] : Sl;
-                Sh = lane == s ? S[s + 1] : Sh;
+                    for (int q = 1; q < G; q++) bs = s == q ? base[q] : bs;
+                    const int newidx = (int)(w >> 17) - (ONE ? bs : (int)kp[cs_live(v) ? start : 0]);
+                    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)unpad((int)(w & 0xFFFFu), PW), rP,
+                                                          keep ? (s * A + newidx) * 2 : kOOB, e0 * A * 2, 0);
+                }
             }
-            nk = (int)kp[Sh] - (int)kp[Sl];
-            had = Sh > Sl;
+            int Sl = T, Sh = T;   // lane s < G: [S[s], S[s+1])
+            int nk = 0;           // lane s < G: the env's new count
+            bool had;             // ... and whether it had agents
+            if (ONE) {
+#pragma unroll
+                for (int s = 0; s < G; s++) nk = lane == s ? base[s + 1] - base[s] : nk;
+                had = cur.c > 0;
+            } else {
+#pragma unroll
+                for (int s = 0; s < G; s++) {
+                    Sl = lane == s ? S[s] : Sl;
+                    Sh = lane == s ? S[s + 1] : Sh;
+                }
+                nk = (int)kp[Sh] - (int)kp[Sl];
+                had = Sh > Sl;
+            }
+            const bool rs = a.auto_reset && lane < nenv && nk == 0;
+            rsm = __ballot(rs);
+            __builtin_amdgcn_raw_buffer_store_b32((unsigned)(rs ? a.N : nk), rC,
+                                                  lane < G && !(PEP && rs) ? lane * 4 : kOOB, e0 * 4, 0);
+            if (rsm) {   // wave-uniform, rare
+                // PEP: an emptied env's count is its own N, read here and stored by the env's lane in
+                // place of the store above (nothing of the record is held for it through the step)
+                if (PEP && rs) a.cnt[e0 + lane] = a.envp[e0 + lane].N;
+                c_resets += (unsigned)__popcll(rsm);
+                if (a.episodes && rs) a.episodes[e0 + lane] += 1;
+                if (!ONE && lane == 0) pend[iter >> 2] |= (uint32_t)rsm << (8 * (iter & 3));
+            }
+            // episode log (episode_log.h): with auto_reset every ended env is in rsm, so the
+            // ballot of ending lanes is taken inside that rare branch only
+            if (EPL && (rsm || !a.auto_reset))
+                eplog_end_wave(a, lane < nenv && nk == 0 && had, rs, e0 + lane, a.t, lane);
+            // ONE: no wave_sync stands before the position stores, so resolve's adds to the tile (other
+            // lanes' LDS atomics) are ordered before the stencil's reads here
+            if (ONE) wave_sync();
         }
-        const bool rs = a.auto_reset && lane < nenv && nk == 0;
-        rsm = __ballot(rs);
-        __builtin_amdgcn_raw_buffer_store_b32((unsigned)(rs ? a.N : nk), rC, lane < G && !(PEP && rs) ? lane * 4 : kOOB, e0 * 4, 0);
-        if (rsm) {   // wave-uniform, rare
-            // PEP: an emptied env's count is its own N, read here and stored by the env's lane in
-            // place of the store above (nothing of the record is held for it through the step)
-            if (PEP && rs) a.cnt[e0 + lane] = a.envp[e0 + lane].N;
-            c_resets += (unsigned)__popcll(rsm);
-            if (a.episodes && rs) a.episodes[e0 + lane] += 1;
-            if (!ONE && lane == 0) pend[iter >> 2] |= (uint32_t)rsm << (8 * (iter & 3));
-        }
-        // episode log (episode_log.h): with auto_reset every ended env is in rsm, so the
-        // ballot of ending lanes is taken inside that rare branch only
-        if (EPL && (rsm || !a.auto_reset))
-            eplog_end_wave(a, lane < nenv && nk == 0 && had, rs, e0 + lane, a.t, lane);
-        // NOKP: the wave_sync that stood before the position stores also ordered resolve's adds to
-        // the tile (other lanes' LDS atomics) before the stencil's reads, so it stands here now
-        if (NOKP) wave_sync();
-        }   // LAD >= 3
 
         // ---- next group's HBM loads, in flight across the stencil, the stores and the
         // next group's head ------------------------------------------------------------
-        if (!ONE && (PF == 0 || LAD < 3)) load(gn, nxt);
+        if (!ONE) load(gn, nxt);
 
-#if FFM_GROUP_PROBE_VALU > 0 || FFM_GROUP_PROBE_SALU > 0
-        {   // diagnostic issue probes (timing only): N extra VALU / SALU instructions per group
-            uint32_t pv = (uint32_t)lane, ps = (uint32_t)g;
-#pragma unroll
-            for (int i = 0; i < FFM_GROUP_PROBE_VALU; i++) asm volatile("v_add_u32 %0, %0, 1" : "+v"(pv));
-#pragma unroll
-            for (int i = 0; i < FFM_GROUP_PROBE_SALU; i++) asm volatile("s_add_u32 %0, %0, 1" : "+s"(ps));
-            asm volatile("" ::"v"(pv), "s"(ps));
-        }
-#endif
         // ---- update_dff (model/ffm_core.py:106-117): B = c0 * D, A = B + sum c1 * B[nb],
         // then the DFF stores (an env reset this step starts its next episode at zero) ----
         if (SCALAR_TAIL) {     // the last, partial float4 slot as one cell per lane (all lanes busy)
@@ -1085,18 +939,13 @@ void core_group_kernel(CoreStepArgs a) {
     }
 }
 
-// one: the single-group form's own size (its carve and block-shared region, kGroupFitCarve).
+// Both forms of the kernel take the same size.
 // room: the room form's (per-env rooms: its own carve, no block-shared region; F the largest room's).
-size_t core_group_smem_bytes(int H, int W, int F, int waves, int G, bool one, bool room) {
+size_t core_group_smem_bytes(int H, int W, int F, int waves, int G, bool room) {
     const int PHW = (H + 2) * (W + 2), TS = lane_tile_floats(H, W);
     if (room)
-        return (size_t)waves * (G == kGroupGSmall ? group_room_carve<kGroupGSmall, kRoomSffLds>(PHW, TS, F).c.per_wave
-                                                  : group_room_carve<kGroupG, kRoomSffLds>(PHW, TS, F).c.per_wave);
-    if (one && kGroupFitCarve) {
-        const size_t per_wave = G == kGroupGSmall ? group_carve<kGroupGSmall, true>(PHW, TS, F).per_wave
-                                                  : group_carve<kGroupG, true>(PHW, TS, F).per_wave;
-        return group_one_shared_bytes(PHW) + (size_t)waves * per_wave;
-    }
+        return (size_t)waves * (G == kGroupGSmall ? group_room_carve<kGroupGSmall>(PHW, TS, F).per_wave
+                                                  : group_room_carve<kGroupG>(PHW, TS, F).per_wave);
     const size_t per_wave = G == kGroupGSmall ? group_carve<kGroupGSmall>(PHW, TS, F).per_wave
                                               : group_carve<kGroupG>(PHW, TS, F).per_wave;
     return group_shared_bytes(PHW, F) + (size_t)waves * per_wave;
@@ -1150,12 +999,11 @@ void core_group_stage_build(int H, int W, int F, const uint8_t* pmap, const floa
 // PEP: the per-env form (a.envp set; a.stage is then the image built with multiplier 1).
 template <int NB, bool KD1, int G, bool PEP = false>
 static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int op, int* occ, bool one) {
-    // each form at its own LDS size
-    const size_t smem = core_group_smem_bytes(a.H, a.W, a.F, 4, G), smem1 = core_group_smem_bytes(a.H, a.W, a.F, 4, G, true);
+    const size_t smem = core_group_smem_bytes(a.H, a.W, a.F, 4, G);
     if (op) {   // the resident blocks per CU of the form `one` names
         *occ = 0;
         const hipError_t r =
-            one ? hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1, false, true, PEP>, 256, smem1)
+            one ? hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1, false, true, PEP>, 256, smem)
                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, KD1, false, false, PEP>, 256, smem);
         if (r != hipSuccess) *occ = 0;
         return hipSuccess;
@@ -1169,8 +1017,8 @@ static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int
     // the single-group form wherever no wave of the grid steps a second group
     const dim3 grid((unsigned)blocks), block(256);
     if (one && core_group_one_group(a.E, blocks, G)) {
-        if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true, true, PEP><<<grid, block, smem1, s>>>(a);
-        else core_group_kernel<NB, 12, 12, G, KD1, false, true, PEP><<<grid, block, smem1, s>>>(a);
+        if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true, true, PEP><<<grid, block, smem, s>>>(a);
+        else core_group_kernel<NB, 12, 12, G, KD1, false, true, PEP><<<grid, block, smem, s>>>(a);
     } else {
         if (a.ep_start) core_group_kernel<NB, 12, 12, G, KD1, true, false, PEP><<<grid, block, smem, s>>>(a);
         else core_group_kernel<NB, 12, 12, G, KD1, false, false, PEP><<<grid, block, smem, s>>>(a);
@@ -1181,7 +1029,7 @@ static hipError_t group_op(const CoreStepArgs& a, int blocks, hipStream_t s, int
 // The room form (a.rooms set): the single-group form only, so the grid holds a wave per group.
 template <int NB, int G>
 static hipError_t group_room_op(const CoreStepArgs& a, int blocks, hipStream_t s, int op, int* occ) {
-    const size_t smem = core_group_smem_bytes(a.H, a.W, a.F, 4, G, true, true);
+    const size_t smem = core_group_smem_bytes(a.H, a.W, a.F, 4, G, true);
     if (op) {
         *occ = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, core_group_kernel<NB, 12, 12, G, false, false, true, true, true>,

@@ -90,9 +90,6 @@ __host__ __device__ inline size_t lane_shared_bytes(int PHW, int F, bool room = 
 
 }  // namespace
 
-#ifndef FFM_LANE_PIPE
-#define FFM_LANE_PIPE 0   // 1: the decide draws of the next pair are computed a pair ahead
-#endif
 #ifndef FFM_LANE_ABLATE
 #define FFM_LANE_ABLATE 0   // diagnostic builds only: bit k replaces / skips one piece (tools/ab_core.sh)
 #endif
@@ -235,9 +232,6 @@ void core_lane_kernel(CoreStepArgs a) {
     uint32_t* const pend = reinterpret_cast<uint32_t*>(wbase + cv.pend);
     if (lane < kLanePendWords) pend[lane] = 0u;
     const int g_first = g;
-#if FFM_LANE_PIPE
-    uint4 pbn = philox(make_uint4(a.t, ebase + (uint32_t)(g * 2 + sub), (uint32_t)al, kPurDecide << 28), a.key0, a.key1);
-#endif
     for (int iter = 0; g < ngroups; g += wstride, iter++) {
         // ---- stage this pair's DFF (loaded by the previous iteration or the prologue) -----
         if (tb0 >= 0) *reinterpret_cast<float4*>(tile + tb0) = cur.d0;
@@ -282,14 +276,10 @@ void core_lane_kernel(CoreStepArgs a) {
 
         LSTAMP(0);
         // ---- decide (model/ffm_core.py:40-88) -------------------------------------------
-#if FFM_LANE_PIPE
-        const uint4 pb = pbn;
-#else
         const uint4 pb = (FFM_LANE_ABLATE & 1)
                              ? make_uint4(genv * 2654435761u ^ (uint32_t)al * 40503u ^ a.t * 97u,
                                           genv ^ (uint32_t)al * 7919u, a.t * 31u ^ genv, (uint32_t)al ^ a.t)
                              : philox(make_uint4(a.t, genv, (uint32_t)al, kPurDecide << 28), a.key0, a.key1);
-#endif
         words[lane] = make_uint2(pb.z, pb.w);   // the friction draw, if this agent owns a contested target
         bool to_exit = false;
         uint32_t slot = (FFM_LANE_ABLATE & 16) ? (uint32_t)NB
@@ -388,11 +378,6 @@ void core_lane_kernel(CoreStepArgs a) {
         // next group's head ------------------------------------------------------------
         LaneState nxt;
         load(g + wstride < ngroups ? g + wstride : -1, nxt);
-#if FFM_LANE_PIPE
-        // the next pair's decide draws: counter-based, so they need no state of this step
-        pbn = philox(make_uint4(a.t, ebase + (uint32_t)((g + wstride) * 2 + sub), (uint32_t)al, kPurDecide << 28),
-                     a.key0, a.key1);
-#endif
 
         LSTAMP(5);
         // ---- update_dff (model/ffm_core.py:106-117): B = c0 * D, A = B + sum c1 * B[nb] -----

@@ -78,9 +78,6 @@
 #ifndef FFM_WAVES_PER_EU
 #define FFM_WAVES_PER_EU 0   // minimum waves/SIMD requested for the wave kernel (0 = compiler's choice)
 #endif
-#ifndef FFM_PREFETCH_LATE
-#define FFM_PREFETCH_LATE 1   // 0: next group's loads at the top; 1: after decide; 2: after resolve
-#endif
 #ifndef FFM_LDS_PAD
 #define FFM_LDS_PAD 0  // diagnostic builds only: extra dynamic LDS per block to pin occupancy
 #endif
@@ -254,15 +251,14 @@ void core_wave_kernel(CoreStepArgs a) {
 #endif
 
     for (; g < ngroups; g += wstride) {
-        // Next group's HBM loads: issued after decide (FFM_PREFETCH_LATE), so that the
-        // prefetch registers are not live across the decide phase (the VGPR peak).
+        // Next group's HBM loads: issued after decide, so that the prefetch registers are
+        // not live across the decide phase (the VGPR peak).
         WavePrefetch nxtpf;
         auto issue_prefetch = [&]() {
             prefetch(((FFM_ABLATE & 8) || ((FFM_ABLATE & 512) && !(FFM_ABLATE & 1024))) ? -1
                                                                                   : (g + wstride < ngroups ? g + wstride : -1),
                      nxtpf);
         };
-        if (!FFM_PREFETCH_LATE) issue_prefetch();
 
         const long long e0 = (long long)g * EW;
         const int nenv = (int)((a.E - e0) < EW ? (a.E - e0) : EW);
@@ -332,7 +328,7 @@ void core_wave_kernel(CoreStepArgs a) {
         wave_sync();
         STAMP(3);
 
-        if (FFM_PREFETCH_LATE == 1) issue_prefetch();
+        issue_prefetch();
 
         // ---- resolve (model/ffm_core.py:90-98) ---------------------------------------
         {
@@ -401,8 +397,6 @@ void core_wave_kernel(CoreStepArgs a) {
         }
         wave_sync();
         STAMP(4);
-
-        if (FFM_PREFETCH_LATE == 2) issue_prefetch();
 
         // ---- exits: order-preserving compaction (model/ffm_core.py:100-102) ---------
         const int nxt = live ? (int)nx[al] : 0;

@@ -1322,8 +1322,8 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     }
     for (size_t i = 0; i < E; i++)
         if (room_of_env[i] < 0 || room_of_env[i] >= n_rooms) return fail(FFM_E_INVALID, "env rooms: room_of_env out of range");
-    if (group_form && std::max(ffm::core_group_smem_bytes(H, W, fmax, 4, 2, true, true),
-                               ffm::core_group_smem_bytes(H, W, fmax, 4, 4, true, true)) > 64 * 1024)
+    if (group_form && std::max(ffm::core_group_smem_bytes(H, W, fmax, 4, 2, true),
+                               ffm::core_group_smem_bytes(H, W, fmax, 4, 4, true)) > 64 * 1024)
         return fail(FFM_E_UNSUPPORTED, "env rooms: the group kernel's LDS has no room for the largest room");
     if (!block_form && !group_form && ffm::core_lane_smem_bytes(H, W, fmax, 4, true) > 64 * 1024)
         return fail(FFM_E_UNSUPPORTED, "env rooms: the lane kernel's LDS has no room for the largest room");

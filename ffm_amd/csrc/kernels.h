@@ -135,8 +135,8 @@ size_t core_lane_smem_bytes(int H, int W, int F, int waves, bool room = false); 
 hipError_t launch_core_lane(const CoreStepArgs& a, int nb, int blocks, hipStream_t s);
 int core_lane_blocks_per_cu(const CoreStepArgs& a, int nb);
 int core_lane_max_pairs_per_wave();
-// one: the single-group form's; room: the room form's (per-env rooms, F the largest room's)
-size_t core_group_smem_bytes(int H, int W, int F, int waves, int G = 4, bool one = false, bool room = false);
+// room: the room form's (per-env rooms, F the largest room's)
+size_t core_group_smem_bytes(int H, int W, int F, int waves, int G = 4, bool room = false);
 bool core_group_supported(int H, int W);
 int core_group_max_iters();
 // The stage image of the group kernel (CoreStepArgs::stage): its size, the float4s of its

@@ -1,10 +1,10 @@
 """The single-group form's compaction without the kept-prefix array (core_group_kernel<.., ONE>).
 
 The form takes the kept prefix at an env's start from the lane that holds it (the popcount of the
-resolve ballots below that packed index), not from an LDS array; the builds FFM_GROUP_FIT=2 and 3
-also take an agent's position from the register of the lane that loaded its dword and read the
-free list from global memory (profiles/lds_fit/: measured, not the product build), and these
-cases cover their boundaries too.  The cases inject counts and positions with Engine.set_state
+resolve ballots below that packed index), not from an LDS array.  Two measured builds also took an
+agent's position from the register of the lane that loaded its dword and read the free list from
+global memory; they were retired from the source (profiles/lds_fit/README.md names their define
+and the commit, 2113d5c, that rebuilds them), and these cases cover their boundaries too.  The cases inject counts and positions with Engine.set_state
 so that the packed prefix S meets every boundary of those paths, then compare exactly, after
 every case's precondition has been asserted on the oracle's own run:
 
@@ -285,8 +285,9 @@ def test_every_single_group_build(monkeypatch, G, nbh, k_D, log):
 @pytest.mark.parametrize("cand", [None, 0])
 def test_placements_of_several_envs_of_one_group(monkeypatch, cand):
     """Several envs of one group empty in one step: the wave places them one after the other,
-    every placed lane reading its cell from the free list (FFM_GROUP_FIT=3: from the image in
-    global memory).  The default candidate pass, and FFM_RESET_CANDIDATES=0 (the full ranking)."""
+    every placed lane reading its cell from the free list (the retired 20 KB-carve build, rebuilt
+    from commit 2113d5c as profiles/lds_fit/README.md says, read it from the image in global
+    memory).  The default candidate pass, and FFM_RESET_CANDIDATES=0 (the full ranking)."""
     state = (_pattern_state, 4)
     ref = _oracle(state, "neumann", 1, 32)
     placed = np.diff(ref["eps_hist"], axis=0) > 0                                    # [T, E]
