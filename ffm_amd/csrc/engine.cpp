@@ -111,6 +111,12 @@ struct ffm_engine {
     long long eplog_cap = 0;
     unsigned long long* d_ephist = nullptr;   // [ephist_bins] histogram, then the summary's slots
     int ephist_bins = 0;
+    // Field statistics (ffm_engine_set_field_stats): null / 0 while off.  They share d_ep_start
+    // with the episode log: it lives while either feature is on.
+    unsigned long long* d_fs_tab = nullptr;   // [fs_slots][fs_classes][fs_stride] (kernels.h ObserveArgs)
+    int32_t* d_fs_cls = nullptr;              // [n_envs] class of every env, or null (one class)
+    int fs_classes = 0, fs_bins = 0, fs_slots = 0, fs_blocks = 0, fs_run = 0;
+    bool fs_lds = false;                      // the observer's form
     // The step plans, one per form (plan() picks), and when each is filled:
     StepPlan create_plan;      // ffm_engine_create: the lane, group, wave or block kernel
     StepPlan pep_plan;         // each ffm_engine_set_env_params: the lane kernel's per-env form on lane and group
@@ -259,6 +265,11 @@ static constexpr int kDefaultStepShards = 2;
 static size_t ep_sum_offset(int bins) { return ((size_t)bins + 15) & ~(size_t)15; }
 static size_t ep_stats_words(int bins) { return ep_sum_offset(bins) + (size_t)ffm::kEpSumSlots * ffm::kEpSumStride; }
 
+// Field statistics on: the observer follows every step launch, and d_ep_start stays.
+static bool field_stats_on(const ffm_engine* e) { return e->d_fs_tab != nullptr; }
+static size_t fs_stride(const ffm_engine* e) { return (size_t)e->HW + 2 * (size_t)e->fs_bins + 1; }
+
+// ep_start_too: unless the field statistics still need it.
 static void free_episode_log(ffm_engine* e, bool ep_start_too) {
     (void)hipFree(e->d_eplog);
     (void)hipFree(e->d_eplog_n);
@@ -268,10 +279,19 @@ static void free_episode_log(ffm_engine* e, bool ep_start_too) {
     e->d_ephist = nullptr;
     e->eplog_cap = 0;
     e->ephist_bins = 0;
-    if (ep_start_too) {
+    if (ep_start_too && !field_stats_on(e)) {
         (void)hipFree(e->d_ep_start);
         e->d_ep_start = nullptr;
     }
+}
+
+static void free_field_stats(ffm_engine* e) {
+    (void)hipFree(e->d_fs_tab);
+    (void)hipFree(e->d_fs_cls);
+    e->d_fs_tab = nullptr;
+    e->d_fs_cls = nullptr;
+    e->fs_classes = e->fs_bins = e->fs_slots = e->fs_blocks = e->fs_run = 0;
+    e->fs_lds = false;
 }
 
 // A plan of the group kernel: envs per group, the one-launch grid and the step shards (empty: one
@@ -395,6 +415,7 @@ static void release(ffm_engine* e) {
     (void)hipFree(e->d_rooms);
     (void)hipFree(e->d_room_of_env);
     free_capture(e);
+    free_field_stats(e);
     free_episode_log(e, true);
     delete e;
 }
@@ -658,13 +679,36 @@ static ffm::CoreStepArgs make_args(ffm_engine* e) {
     return a;
 }
 
+// The field statistics' observer (core_observe.hip) after the step launch `a` describes: that
+// launch's envs (e0: its first env, for the class array), its step index, its stream.
+static hipError_t launch_observer(const ffm_engine* e, const ffm::CoreStepArgs& a, long long e0, hipStream_t s) {
+    ffm::ObserveArgs o{};
+    o.pos = a.pos;
+    o.cnt = a.cnt;
+    o.ep_start = a.ep_start;
+    o.cls = e->d_fs_cls ? e->d_fs_cls + e0 : nullptr;
+    o.tab = e->d_fs_tab;
+    o.E = a.E;
+    o.A = a.A;
+    o.HW = a.HW;
+    o.bins = e->fs_bins;
+    o.C = e->fs_classes;
+    o.S = (int)fs_stride(e);
+    o.slots = e->fs_slots;
+    o.t = a.t;
+    o.run = e->fs_run;
+    return ffm::launch_core_observe(o, e->fs_lds, e->fs_blocks, s);
+}
+
 // Shards a step(n > 1) call runs as, under the engine's current settings: 1 (one launch per
 // step over all envs) with trajectory capture on (its kernel follows every step launch on the
 // caller's stream), on the fused multi-step path and with per-env parameters on the lane kernel
 // (only plans of the group kernel hold shards; its per-env and room forms hold their own).
+// Field statistics keep the shards (the observer follows each shard's launch on that shard's
+// stream) and keep the engine off the fused path.
 static int shards_in_effect(const ffm_engine* e) {
     const size_t S = plan(e).shards.size();
-    if (S <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi && !rooms_on(e))) return 1;
+    if (S <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi && !rooms_on(e) && !field_stats_on(e))) return 1;
     return (int)S;
 }
 
@@ -700,6 +744,8 @@ static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
             a.counters = base.counters + 4 * sh.ctr0;
             a.no_step_count = k != 0;   // one shard per step counts the step
             he = ffm::launch_core_group(a, e->d.neighborhood, sh.blocks, k ? e->sh_stream[k - 1] : s, sh.g, p.one);
+            // the shards add to the same slot copies: every add to them is an atomic
+            if (he == hipSuccess && field_stats_on(e)) he = launch_observer(e, a, sh.e0, k ? e->sh_stream[k - 1] : s);
         }
     }
     // the join also after a failed launch: what was enqueued stays ordered before the caller's next work
@@ -718,7 +764,7 @@ static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
 int ffm_engine_step(ffm_engine* e, int32_t n_steps, void* stream) {
     if (!e || n_steps < 0) return fail(FFM_E_INVALID, "bad engine/n_steps");
     hipStream_t s = (hipStream_t)stream;
-    if (e->fused > 1 && e->multi && e->cap.n_sel == 0 && !rooms_on(e)) {
+    if (e->fused > 1 && e->multi && e->cap.n_sel == 0 && !rooms_on(e) && !field_stats_on(e)) {
         // k steps per launch, the state of each env pair on chip (core_multi.hip)
         for (int done = 0; done < n_steps;) {
             const int k = std::min(e->fused, n_steps - done);
@@ -749,6 +795,7 @@ int ffm_engine_step(ffm_engine* e, int32_t n_steps, void* stream) {
         case StepPlan::kBlock: HIP_TRY(ffm::launch_core_block(a, e->d.neighborhood, e->f64, e->mt, e->block, s)); break;
         }
         if (e->cap.n_sel) HIP_TRY(ffm::launch_core_capture(a, e->cap, s));
+        if (field_stats_on(e)) HIP_TRY(launch_observer(e, a, 0, s));
         e->t++;
     }
     return FFM_OK;
@@ -991,7 +1038,7 @@ int ffm_engine_set_episode_log(ffm_engine* e, int64_t capacity_records, int32_t 
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipStreamSynchronize(s));        // queued steps may still write the old buffers
     const bool off = capacity_records == 0 && hist_bins == 0;
-    free_episode_log(e, off);
+    free_episode_log(e, off);   // (ep_start stays while the field statistics are on)
     if (off) return FFM_OK;
     hipError_t he = hipSuccess;
     const bool fresh = e->d_ep_start == nullptr;
@@ -1066,6 +1113,133 @@ int ffm_engine_get_episode_stats(ffm_engine* e, uint64_t* hist, int32_t bins, ui
         }
         summary[3] = summary[0] ? ~inv_min : 0;   // no episode yet: min reads 0
     }
+    return FFM_OK;
+}
+
+// A/B switch of the field statistics with a positive integer value (read when the feature is set).
+static int fs_env_int(const char* name, int dflt, int lo, int hi) {
+    if (const char* ov = std::getenv(name)) {
+        const int v = std::atoi(ov);
+        if (v >= lo && v <= hi) return v;
+    }
+    return dflt;
+}
+
+int ffm_engine_set_field_stats(ffm_engine* e, const int32_t* class_of_env, int32_t n_classes, int32_t curve_bins,
+                               void* stream) {
+    if (!e) return fail(FFM_E_INVALID, "null engine");
+    if (e->mt) return fail(FFM_E_UNSUPPORTED, "field statistics: Philox engines only");
+    if (n_classes < 0 || curve_bins < 0) return fail(FFM_E_INVALID, "field statistics: negative class or bin count");
+    hipStream_t s = (hipStream_t)stream;
+    if (n_classes == 0) {
+        HIP_TRY(hipStreamSynchronize(s));    // queued observers may still write the tables
+        free_field_stats(e);
+        if (!e->d_eplog && !e->d_ephist) free_episode_log(e, true);   // ep_start: the log is off too
+        return FFM_OK;
+    }
+    const size_t E = (size_t)e->d.n_envs;
+    if (class_of_env)
+        for (size_t i = 0; i < E; i++)
+            if (class_of_env[i] < 0 || class_of_env[i] >= n_classes)
+                return fail(FFM_E_INVALID, "field statistics: class_of_env entry outside [0, n_classes)");
+    // one copy of the tables as u64, against FFM_FIELD_STATS_MAX_BYTES
+    const size_t S = (size_t)e->HW + 2 * (size_t)curve_bins + 1;
+    const size_t words = (size_t)n_classes * S;
+    if (words * 8 > (size_t)FFM_FIELD_STATS_MAX_BYTES)
+        return fail(FFM_E_INVALID, "field statistics: n_classes * (H * W + 2 * curve_bins + 1) * 8 exceeds "
+                                   "FFM_FIELD_STATS_MAX_BYTES");
+    // The form.  FFM_FIELD_STATS_FORM=lds|global forces one (A/B and test switch, read here).
+    const int blocks = fs_env_int("FFM_FIELD_STATS_BLOCKS", ffm::kObserveMaxBlocks, 1, 65535);
+    const int run = fs_env_int("FFM_FIELD_STATS_RUN", ffm::core_observe_run(e->d.agent_capacity), 1, 4096);
+    const bool fits = words * 4 <= ffm::kObserveLdsBudget &&
+                      ffm::core_observe_lds_safe(e->d.n_envs, e->d.agent_capacity, run, blocks);
+    bool lds = fits;
+    if (const char* ov = std::getenv("FFM_FIELD_STATS_FORM")) {
+        if (!std::strcmp(ov, "lds")) {
+            if (!fits) return fail(FFM_E_INVALID, "field statistics: FFM_FIELD_STATS_FORM=lds, but the tables exceed the LDS budget");
+            lds = true;
+        } else if (!std::strcmp(ov, "global")) {
+            lds = false;
+        }
+    }
+    // slot copies: a power of two, fewer where the copies together would pass the limit
+    int slots = 1;
+    while (slots * 2 <= fs_env_int("FFM_FIELD_STATS_SLOTS", ffm::kObserveSlots, 1, 1024)) slots *= 2;
+    while (slots > 1 && words * 8 * (size_t)slots > (size_t)FFM_FIELD_STATS_MAX_BYTES) slots /= 2;
+
+    HIP_TRY(hipStreamSynchronize(s));        // queued observers may still write the old tables
+    // Build into locals; the engine changes after the last call that can fail.
+    unsigned long long* tab = nullptr;
+    int32_t* cls = nullptr;
+    uint32_t* ep_start = nullptr;
+    const bool fresh = e->d_ep_start == nullptr;
+    const size_t Ep = (E + 7) & ~(size_t)7;   // padded like d_cnt
+    hipError_t he = hipMalloc((void**)&tab, words * 8 * (size_t)slots);
+    if (he == hipSuccess && class_of_env) he = hipMalloc((void**)&cls, E * 4);
+    if (he == hipSuccess && fresh) he = hipMalloc((void**)&ep_start, Ep * 4);
+    const bool nomem = he != hipSuccess;
+    if (he == hipSuccess) he = hipMemsetAsync(tab, 0, words * 8 * (size_t)slots, s);
+    if (he == hipSuccess && cls) he = hipMemcpyAsync(cls, class_of_env, E * 4, hipMemcpyHostToDevice, s);
+    // Turned on mid-run: episodes in flight count from here, as the episode log's do (the next
+    // step is keyed e->t, so the index that "placed" every env is the one before it).
+    if (he == hipSuccess && fresh) he = hipMemsetD32Async((hipDeviceptr_t)ep_start, (int)(e->t - 1u), Ep, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    if (he != hipSuccess) {
+        (void)hipFree(tab);
+        (void)hipFree(cls);
+        (void)hipFree(ep_start);
+        return fail(nomem ? FFM_E_NOMEM : FFM_E_HIP, std::string("field statistics: ") + hipGetErrorString(he));
+    }
+    free_field_stats(e);
+    e->d_fs_tab = tab;
+    e->d_fs_cls = cls;
+    if (fresh) e->d_ep_start = ep_start;
+    e->fs_classes = n_classes;
+    e->fs_bins = curve_bins;
+    e->fs_slots = slots;
+    e->fs_blocks = blocks;
+    e->fs_run = run;
+    e->fs_lds = lds;
+    return FFM_OK;
+}
+
+int ffm_engine_get_field_stats(ffm_engine* e, uint64_t* occupancy, uint64_t* observed, uint64_t* remaining,
+                               uint64_t* alive, int32_t clear, void* stream) {
+    if (!e) return fail(FFM_E_INVALID, "null engine");
+    if (!field_stats_on(e)) return fail(FFM_E_INVALID, "field statistics are off");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t S = fs_stride(e), C = (size_t)e->fs_classes, HW = (size_t)e->HW, bins = (size_t)e->fs_bins;
+    const size_t words = C * S;
+    std::vector<unsigned long long> h(words * (size_t)e->fs_slots);
+    HIP_TRY(hipMemcpyAsync(h.data(), e->d_fs_tab, h.size() * 8, hipMemcpyDeviceToHost, s));
+    if (clear) HIP_TRY(hipMemsetAsync(e->d_fs_tab, 0, h.size() * 8, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int k = 1; k < e->fs_slots; k++)
+        for (size_t i = 0; i < words; i++) h[i] += h[(size_t)k * words + i];
+    for (size_t c = 0; c < C; c++) {
+        const unsigned long long* T = h.data() + c * S;
+        if (occupancy) std::copy(T, T + HW, occupancy + c * HW);
+        if (remaining) std::copy(T + HW, T + HW + bins, remaining + c * bins);
+        if (alive) std::copy(T + HW + bins, T + HW + 2 * bins, alive + c * bins);
+        if (observed) observed[c] = T[HW + 2 * bins];
+    }
+    return FFM_OK;
+}
+
+// Diagnostic (not part of the ABI header): the field statistics in effect.
+//   out[0] 0 off, 1 the LDS form, 2 the global form;  out[1] blocks of the observer's grid over all
+//   envs;  out[2] slot copies of the tables;  out[3] classes;  out[4] curve bins
+int ffm_debug_field_stats_info(ffm_engine* e, int32_t* out, int n) {
+    if (!e || !out || n < 0 || n > 5) return fail(FFM_E_INVALID, "bad args");
+    const bool on = field_stats_on(e);
+    const int32_t v[5] = {
+        !on ? 0 : e->fs_lds ? 1 : 2,
+        on ? ffm::core_observe_grid(e->d.n_envs, e->fs_run, e->fs_blocks) : 0,
+        e->fs_slots,
+        e->fs_classes,
+        e->fs_bins,
+    };
+    for (int i = 0; i < n; i++) out[i] = v[i];
     return FFM_OK;
 }
 

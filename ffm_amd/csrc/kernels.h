@@ -127,6 +127,37 @@ struct CoreCapture {
     int n_sel, period;
 };
 
+// Field statistics (ffm_engine_set_field_stats; core_observe.hip): what the observer launched after
+// a step launch reads -- that launch's slices of pos, cnt, ep_start and the class array -- and the
+// tables it adds to.  One class's table is S = HW + 2 bins + 1 words: occupancy[HW],
+// remaining[bins], alive[bins], observed; `tab` holds `slots` (a power of two) copies of the C
+// tables, summed by the host when it reads.
+struct ObserveArgs {
+    const uint16_t* pos;           // [E][A]
+    const int* cnt;                // [E]
+    const uint32_t* ep_start;      // [E]
+    const int* cls;                // [E] class of every env, or nullptr (class 0)
+    unsigned long long* tab;       // [slots][C][S]
+    long long E;
+    int A, HW, bins, C, S, slots;
+    uint32_t t;                    // the step index that keyed the step launch
+    int run;                       // envs per run (core_observe_run)
+};
+// The observer's LDS budget: the C tables as u32 take the LDS form where they fit it.  A workgroup
+// may declare up to 160 KiB on gfx950, but 64 KiB keeps two blocks of the observer per CU next to
+// whatever a neighbouring shard's step kernel holds, and needs no opt-in above the default limit.
+constexpr size_t kObserveLdsBudget = 64 * 1024;
+// Slot copies of the tables, the observer's largest grid and the envs of a run (FFM_FIELD_STATS_SLOTS,
+// _BLOCKS and _RUN override them when the feature is set: A/B and test switches; profiles/field_stats/).
+// Measured at C2 (two shards of 32,768 envs): 64 to 256 blocks per launch all add 7.1 - 7.7 us to the
+// step, 512 blocks 12.7 us and 2,048 blocks 27.8 us (every block zeroes and flushes its tables);
+// 1, 4, 16 and 64 slots are within 0.5 us of each other.
+constexpr int kObserveSlots = 16, kObserveMaxBlocks = 256;
+int core_observe_run(int A);   // the default run: one batch of cell pairs per thread
+int core_observe_grid(long long E, int run, int max_blocks);
+bool core_observe_lds_safe(long long E, int A, int run, int max_blocks);
+hipError_t launch_core_observe(const ObserveArgs& o, bool lds, int max_blocks, hipStream_t s);
+
 size_t core_wave_smem_bytes(int H, int W, int A, int F, bool mt, bool reset, int waves);
 size_t core_block_smem_bytes(int H, int W, int A, int K, int F, bool f64, bool mt, bool reset);
 hipError_t launch_core_wave(const CoreStepArgs& a, int nb, bool mt, int blocks, hipStream_t s);

@@ -30,6 +30,7 @@ EXPORTED = [
     "ffm_engine_set_step_index", "ffm_engine_set_fused_steps", "ffm_np_expf_device",
     "ffm_engine_set_trajectory_capture", "ffm_engine_drain_trajectory",
     "ffm_engine_set_episode_log", "ffm_engine_drain_episodes", "ffm_engine_get_episode_stats",
+    "ffm_engine_set_field_stats", "ffm_engine_get_field_stats",
     "ffm_debug_stage_image", "ffm_debug_reset_candidates",
     "ffm_engine_set_env_params", "ffm_engine_get_env_params", "ffm_engine_set_env_params_kernel",
     "ffm_engine_set_env_rooms", "ffm_engine_get_env_rooms", "ffm_engine_set_env_rooms_kernel",
@@ -150,6 +151,8 @@ def load_library():
     L.ffm_engine_set_episode_log.argtypes = [P, i64, i32, P]
     L.ffm_engine_drain_episodes.argtypes = [P, P, i64, C.POINTER(i64), C.POINTER(i64), P]
     L.ffm_engine_get_episode_stats.argtypes = [P, P, i32, P, i32, P]
+    L.ffm_engine_set_field_stats.argtypes = [P, P, i32, i32, P]
+    L.ffm_engine_get_field_stats.argtypes = [P, P, P, P, P, i32, P]
     L.ffm_engine_set_env_params.argtypes = [P, C.POINTER(EnvParams), i32, P, P]
     L.ffm_engine_get_env_params.argtypes = [P, C.POINTER(EnvParams), i32, C.POINTER(i32), P]
     L.ffm_engine_set_env_params_kernel.argtypes = [P, i32]
@@ -614,6 +617,42 @@ class Engine:
         return {"count": cnt, "sum": tot, "sum_sq": sq, "min": int(s[3]), "max": int(s[4]), "mean": mean,
                 "std": var ** 0.5, "hist": hist}
 
+    # -- field statistics --------------------------------------------------------
+    def set_field_stats(self, classes=None, n_classes: int | None = None, curve_bins: int = 0, stream=None):
+        """Sum, on the device and per class of envs, where the crowd stands and how the room
+        empties (what the reference reads off the positions main.py:44-54 logs every step); see
+        ffm_engine_set_field_stats.  `classes`: n_envs class indices (None: every env in class
+        0); `n_classes`: None = max(classes) + 1 (one class without `classes`), 0 = off;
+        `curve_bins` > 0 adds the curves `remaining` and `alive` over the steps since placement
+        (the last bin holds every later step).  While on, step(n) takes one launch per step (no
+        fused steps) and an observer launch follows each; read with field_stats()."""
+        cls = None
+        if classes is not None:
+            cls = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1)
+            if cls.size != self.n_envs:
+                raise ValueError(f"classes must have n_envs = {self.n_envs} entries, got {cls.size}")
+        if n_classes is None:
+            n_classes = 1 if cls is None else int(cls.max()) + 1
+        _check(self._L.ffm_engine_set_field_stats(self._h, _ptr(cls), int(n_classes), int(curve_bins),
+                                                  _stream_handle(stream)))
+        self._fs_shape = (int(n_classes), int(curve_bins))
+
+    def field_stats(self, clear: bool = False, stream=None) -> dict:
+        """The field statistics as uint64 arrays: occupancy [C, H, W] (visits of every cell),
+        observed [C] (env states observed), remaining [C, bins] (agents inside, by steps since
+        placement) and alive [C, bins] (env states, by steps since placement); the curves are
+        empty without curve_bins.  occupancy / observed is a cell's mean density; remaining[tau]
+        over the number of episodes is the mean number inside at tau.  clear=True zeroes them
+        after the read."""
+        c, bins = getattr(self, "_fs_shape", (0, 0))
+        occ = np.zeros((c, self.H, self.W), np.uint64)
+        obs = np.zeros(c, np.uint64)
+        rem = np.zeros((c, bins), np.uint64)
+        alive = np.zeros((c, bins), np.uint64)
+        _check(self._L.ffm_engine_get_field_stats(self._h, _ptr(occ), _ptr(obs), _ptr(rem), _ptr(alive),
+                                                  int(bool(clear)), _stream_handle(stream)))
+        return {"occupancy": occ, "observed": obs, "remaining": rem, "alive": alive}
+
     def run_episodes(self, per_env: int = 1, max_steps: int | None = None, chunk: int = 16, stream=None) -> np.ndarray:
         """Step until every env has logged `per_env` episodes and return their lengths, int32
         [E, per_env] indexed by episode (counted from the last reset()): E replicas of
@@ -751,12 +790,22 @@ class Engine:
         group kernel's single-group form ("group_one"; False: its loop form, or another kernel).
         "env_rooms": the room count of set_env_rooms(), 0 while off (on: the lane kernel, or with
         kernel="block" the block kernel, one shard each; with kernel="group" the group kernel,
-        "group_one" True, with that form's own blocks and shards)."""
+        "group_one" True, with that form's own blocks and shards).
+        "field_stats": "off", or with set_field_stats() on a dict of the observer's form ("lds" or
+        "global"), its grid's blocks over all envs, the tables' slot copies, the classes and the
+        curve bins."""
         v = np.zeros(10, np.int32)
         _check(self._L.ffm_debug_launch_info(self._h, _ptr(v), len(v)))
         rooms = C.c_int32()
         _check(self._L.ffm_engine_get_env_rooms(self._h, None, None, 0, C.byref(rooms), None))
-        return {"env_rooms": int(rooms.value),
+        # bound here, as group_occupancy()'s: a diagnostic outside the ABI header
+        fs = np.zeros(5, np.int32)
+        fn = self._L.ffm_debug_field_stats_info
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_int], C.c_int
+        _check(fn(self._h, _ptr(fs), len(fs)))
+        field_stats = "off" if fs[0] == 0 else {"form": ("lds", "global")[int(fs[0]) - 1], "blocks": int(fs[1]),
+                                                "slots": int(fs[2]), "classes": int(fs[3]), "curve_bins": int(fs[4])}
+        return {"env_rooms": int(rooms.value), "field_stats": field_stats,
                 "kernel": ("group", "lane", "wave", "block", "block_scratch")[int(v[0])], "group_g": int(v[1]),
                 "blocks": int(v[2]), "K": int(v[3]), "block_size": int(v[4]), "multi": bool(v[5]),
                 "multi_blocks": int(v[6]), "step_shards": int(v[7]), "shard_blocks": int(v[8]),

@@ -43,6 +43,18 @@ floor field (``data.geodesic_sff``) instead of the L1 distance; on rooms without
 are the same bits.
 
     python -m ffm_amd.evac --room 50 50 --N 100 --sweep exit_width=1,2,4 --envs 1024 --out runs/rooms50
+
+``--fields`` adds what the reference reads off its per-step position log (``main.py:44-54``,
+``visualize_trajectory.py``): where the crowd stands and how the room empties, summed on the device
+(``Engine.set_field_stats``) with one class per sweep combination (one class without a sweep).  It
+writes ``occupancy.npy`` ([P, H, W] uint64 visits of every cell), ``occupancy.csv``
+(``set,row,col,occupancy``, the cells ever occupied), ``observed.csv`` (``set,observed``: divide a
+set's map by it for the mean density) and, with ``--curve-bins B``, ``remaining.csv``
+(``set,tau,remaining,alive``: agents inside and envs still evacuating tau steps after placement).
+With ``--episodes`` > 1 an env that finishes early keeps evacuating until the slowest is done, and
+those episodes are observed too: normalise by ``observed`` and ``alive``, not by ``--episodes``.
+
+    python -m ffm_amd.evac --room 12 12 --sweep exit_width=1,2,4 --fields --curve-bins 128 --envs 4096 --out runs/fields
 """
 from __future__ import annotations
 
@@ -203,6 +215,39 @@ def summary_text(steps: np.ndarray, total_steps: int, seconds: float) -> str:
             f"steps_per_second {rate:.1f}\n")
 
 
+def observed_csv(observed) -> str:
+    """The text of observed.csv from Engine.field_stats()["observed"] [P]: ``set,observed``, the
+    env states each set's occupancy map sums (occupancy / observed is a cell's mean density)."""
+    obs = np.asarray(observed).reshape(-1)
+    return "\n".join(["set,observed"] + [f"{p},{int(v)}" for p, v in enumerate(obs.tolist())]) + "\n"
+
+
+def occupancy_csv(occupancy) -> str:
+    """The text of occupancy.csv from Engine.field_stats()["occupancy"] [P, H, W]:
+    ``set,row,col,occupancy``, one row per cell that was ever occupied, in (set, row, col) order
+    (occupancy.npy holds the whole array)."""
+    occ = np.asarray(occupancy)
+    lines = ["set,row,col,occupancy"]
+    for p, x, y in np.argwhere(occ != 0).tolist():
+        lines.append(f"{p},{x},{y},{int(occ[p, x, y])}")
+    return "\n".join(lines) + "\n"
+
+
+def remaining_csv(remaining, alive) -> str:
+    """The text of remaining.csv from Engine.field_stats()' curves [P, bins]:
+    ``set,tau,remaining,alive`` for every set and every tau = 0 .. bins - 1 (tau: steps since the
+    placement; the last holds every later step too; tau = 0, the placement, is never observed).
+    remaining / episodes is the mean number inside at tau, its slope the outflow."""
+    rem, al = np.asarray(remaining), np.asarray(alive)
+    if rem.shape != al.shape or rem.ndim != 2:
+        raise ValueError("remaining and alive are [sets, bins] arrays of one shape")
+    lines = ["set,tau,remaining,alive"]
+    for p in range(rem.shape[0]):
+        for tau in range(rem.shape[1]):
+            lines.append(f"{p},{tau},{int(rem[p, tau])},{int(al[p, tau])}")
+    return "\n".join(lines) + "\n"
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--map", help=".npy map (0 free, 2 wall, 3 exit)")
@@ -232,6 +277,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="the kernel that steps a room sweep (Engine.set_env_rooms' kernel): lane, the group kernel's "
                          "own room form (12x12 engines, opt-in) or block (default: the driver's pick, "
                          "room_sweep_kernel; same outputs whichever runs)")
+    ap.add_argument("--fields", action="store_true",
+                    help="also write the on-device field statistics (Engine.set_field_stats), one class per sweep "
+                         "combination: occupancy.npy, occupancy.csv, observed.csv")
+    ap.add_argument("--curve-bins", type=int, default=0, metavar="B",
+                    help="with --fields: the evacuation curve over tau = 0 .. B - 1 steps since placement "
+                         "(remaining.csv)")
     ap.add_argument("--out", required=True, metavar="DIR")
     return ap
 
@@ -239,6 +290,8 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
+    if a.curve_bins < 0 or (a.curve_bins and not a.fields):
+        ap.error("--curve-bins B wants B >= 0 and --fields")
     if sum(map(bool, (a.map, a.room, a.rooms))) != 1 or (a.rooms and a.sff):
         ap.error("give either --map and --sff, or --room H W, or --rooms MAP.npy:SFF.npy ...")
     try:
@@ -305,14 +358,26 @@ def main(argv=None):
         eng.close()
         ap.error(str(err))
     eng.set_episode_log(hist_bins=0)
+    if a.fields:   # the class is the sweep's combination index
+        eng.set_field_stats(classes=soe if sets else None, n_classes=len(sets) if sets else 1,
+                            curve_bins=a.curve_bins)
     eng.reset()
     t0 = time.perf_counter()
     steps = eng.run_episodes(per_env=a.episodes, max_steps=a.max_steps)
     dt = time.perf_counter() - t0
     taken = eng.counters()["steps"]
+    fields = eng.field_stats() if a.fields else None
     eng.close()
 
     os.makedirs(a.out, exist_ok=True)
+    if fields is not None:
+        np.save(os.path.join(a.out, "occupancy.npy"), fields["occupancy"])
+        texts = {"occupancy.csv": occupancy_csv(fields["occupancy"]), "observed.csv": observed_csv(fields["observed"])}
+        if a.curve_bins > 0:
+            texts["remaining.csv"] = remaining_csv(fields["remaining"], fields["alive"])
+        for name, body in texts.items():
+            with open(os.path.join(a.out, name), "w") as f:
+                f.write(body)
     with open(os.path.join(a.out, "steps_per_episode.csv"), "w") as f:
         f.write(steps_csv(records_from_steps(steps), a.episodes, a.N, sets, soe))
     if sets:

@@ -232,6 +232,53 @@ int ffm_engine_drain_episodes(ffm_engine* eng, int32_t* records, int64_t cap, in
 int ffm_engine_get_episode_stats(ffm_engine* eng, uint64_t* hist, int32_t bins, uint64_t* summary, int32_t clear,
                                  void* stream);
 
+/* Field statistics: where the crowd stands and how the room empties, summed on the device.
+ * The reference gets both from the positions it logs after every step (main.py:44-54, read
+ * back by visualize_trajectory.py and inspect_trajectory.py); here an observer kernel follows
+ * every step launch and no position leaves the device.
+ *
+ * Env e has a class, class_of_env[e] in [0, n_classes) (NULL: every env in class 0).  Per class
+ * c the engine keeps four arrays of u64:
+ *   occupancy[c][H * W]   visits of every cell (row-major cell indices, as ffm_engine_get_state's)
+ *   observed[c]           observed env states
+ *   remaining[c][bins]    agents inside, by time since placement   (bins = curve_bins > 0)
+ *   alive[c][bins]        observed env states, by time since placement
+ * After every step launch keyed t, for every env e of it: n = counts[e], tau = t - ep_start[e]
+ * in wrapping u32 (the episode log's ep_start and arithmetic).  n == 0 adds nothing; tau == 0
+ * adds nothing (this step's auto-reset placed the env: a placement is never observed, whether
+ * ffm_engine_reset, ffm_engine_reset_envs or the auto-reset made it, so an episode of T steps
+ * adds exactly its states tau = 1 .. T - 1).  Otherwise, with b = min(tau, bins - 1):
+ *   occupancy[c][positions[e][j]] += 1 for j < n;  observed[c] += 1;
+ *   remaining[c][b] += n;  alive[c][b] += 1.
+ * The mean density of a cell is occupancy / observed; the mean number inside at tau is
+ * remaining[tau] divided by the number of episodes: both divisions are the caller's.  Every sum
+ * is an integer: the same bits under any launch geometry, step shards, the fused-steps setting
+ * and either form of the observer (FFM_FIELD_STATS_FORM=lds|global, read by this call, forces
+ * one; lds on tables beyond the LDS budget: FFM_E_INVALID).  The step itself does not change.
+ *
+ * n_classes == 0 turns the feature off and frees everything.  FFM_E_INVALID, the engine exactly
+ * as it was: n_classes < 0, curve_bins < 0, a class outside [0, n_classes), or tables of more
+ * than FFM_FIELD_STATS_MAX_BYTES (one copy: n_classes * (H * W + 2 * curve_bins + 1) * 8 bytes).
+ * Philox only (MT: FFM_E_UNSUPPORTED).  Setting it again replaces classes and bins and clears.
+ *
+ * While on, ffm_engine_step takes one launch per step (the fused multi-step path is not taken,
+ * as with trajectory capture; the state is the same bits) and the observer follows each, on
+ * each step shard's own stream where shards are in effect (measured on one MI355X at 65,536 envs
+ * of 12x12 with 32 agents: 22.8 us per step off, 30.4 us with five classes and 128 bins, 87.9 us
+ * with the global form forced; profiles/field_stats/).  ffm_engine_reset clears nothing
+ * (`clear` below, or turning the feature off, does).  Turned on mid-run, episodes in flight
+ * count from the steps taken after the call.  ffm_engine_set_step_index inside an episode, and
+ * ffm_engine_set_state with new counts, leave the affected tau undefined.  Synchronises the
+ * stream. */
+#define FFM_FIELD_STATS_MAX_BYTES (256ll << 20)
+int ffm_engine_set_field_stats(ffm_engine* eng, const int32_t* class_of_env, int32_t n_classes, int32_t curve_bins,
+                               void* stream);
+/* occupancy[C][H * W], observed[C], remaining[C][bins], alive[C][bins] to the host (any may be
+ * NULL).  clear != 0 zeroes them afterwards.  Feature off: FFM_E_INVALID.  Synchronises the
+ * stream. */
+int ffm_engine_get_field_stats(ffm_engine* eng, uint64_t* occupancy, uint64_t* observed, uint64_t* remaining,
+                               uint64_t* alive, int32_t clear, void* stream);
+
 /* Per-env parameters and agent counts: a whole sweep in one engine.  Replaces the user's loop
  * over FloorFieldModel(params=...) instances, one per point of an evacuation-time-against-N
  * curve (analyze_steps_by_n.py) or of the (k_S, k_D) plane -- each far too small to fill the
