@@ -117,6 +117,18 @@ struct ffm_engine {
     int32_t* d_fs_cls = nullptr;              // [n_envs] class of every env, or null (one class)
     int fs_classes = 0, fs_bins = 0, fs_slots = 0, fs_blocks = 0, fs_run = 0;
     bool fs_lds = false;                      // the observer's form
+    // Exit flow (ffm_engine_set_exit_flow): null / 0 / empty while off.  It shares d_ep_start with
+    // the episode log and the field statistics: it lives while any of the three is on.
+    unsigned long long* d_xf_tab = nullptr;   // [xf_slots][xf_classes][xf_doors][1 + xf_bins] (kernels.h FlowArgs)
+    int32_t* d_xf_cls = nullptr;              // [n_envs] class of every env, or null (one class)
+    uint8_t* d_xf_door_from = nullptr;        // [rooms][HW] the door table
+    uint16_t* d_prev_pos = nullptr;           // the snapshot of pos, cnt and ep_start before the next step,
+    int32_t* d_prev_cnt = nullptr;            // sized like them
+    uint32_t* d_prev_start = nullptr;
+    int xf_classes = 0, xf_doors = 0, xf_bins = 0, xf_slots = 0, xf_blocks = 0, xf_rooms = 0;
+    bool xf_lds = false;                      // the flow kernel's form
+    std::vector<int32_t> xf_door_of_cell;     // [rooms][HW] the labels in effect, -1 off the exits
+    std::vector<uint8_t> map0;                // the create-time map, row-major (0 free, 2 blocked, 3 exit)
     // The step plans, one per form (plan() picks), and when each is filled:
     StepPlan create_plan;      // ffm_engine_create: the lane, group, wave or block kernel
     StepPlan pep_plan;         // each ffm_engine_set_env_params: the lane kernel's per-env form on lane and group
@@ -268,8 +280,13 @@ static size_t ep_stats_words(int bins) { return ep_sum_offset(bins) + (size_t)ff
 // Field statistics on: the observer follows every step launch, and d_ep_start stays.
 static bool field_stats_on(const ffm_engine* e) { return e->d_fs_tab != nullptr; }
 static size_t fs_stride(const ffm_engine* e) { return (size_t)e->HW + 2 * (size_t)e->fs_bins + 1; }
+// Exit flow on: the flow kernel follows every step launch, and d_ep_start stays.
+static bool exit_flow_on(const ffm_engine* e) { return e->d_xf_tab != nullptr; }
+static size_t xf_words(const ffm_engine* e) { return (size_t)e->xf_classes * e->xf_doors * (1 + (size_t)e->xf_bins); }
+// Either follows every step launch with a kernel of its own, which keeps the engine off the fused path.
+static bool observers_on(const ffm_engine* e) { return field_stats_on(e) || exit_flow_on(e); }
 
-// ep_start_too: unless the field statistics still need it.
+// ep_start_too: unless the field statistics or the exit flow still need it.
 static void free_episode_log(ffm_engine* e, bool ep_start_too) {
     (void)hipFree(e->d_eplog);
     (void)hipFree(e->d_eplog_n);
@@ -279,10 +296,24 @@ static void free_episode_log(ffm_engine* e, bool ep_start_too) {
     e->d_ephist = nullptr;
     e->eplog_cap = 0;
     e->ephist_bins = 0;
-    if (ep_start_too && !field_stats_on(e)) {
+    if (ep_start_too && !observers_on(e)) {
         (void)hipFree(e->d_ep_start);
         e->d_ep_start = nullptr;
     }
+}
+
+static void free_exit_flow(ffm_engine* e) {
+    void* bufs[] = {e->d_xf_tab, e->d_xf_cls, e->d_xf_door_from, e->d_prev_pos, e->d_prev_cnt, e->d_prev_start};
+    for (void* p : bufs) (void)hipFree(p);
+    e->d_xf_tab = nullptr;
+    e->d_xf_cls = nullptr;
+    e->d_xf_door_from = nullptr;
+    e->d_prev_pos = nullptr;
+    e->d_prev_cnt = nullptr;
+    e->d_prev_start = nullptr;
+    e->xf_classes = e->xf_doors = e->xf_bins = e->xf_slots = e->xf_blocks = e->xf_rooms = 0;
+    e->xf_lds = false;
+    e->xf_door_of_cell.clear();
 }
 
 static void free_field_stats(ffm_engine* e) {
@@ -416,6 +447,7 @@ static void release(ffm_engine* e) {
     (void)hipFree(e->d_room_of_env);
     free_capture(e);
     free_field_stats(e);
+    free_exit_flow(e);
     free_episode_log(e, true);
     delete e;
 }
@@ -452,6 +484,8 @@ int ffm_engine_create(const ffm_engine_desc* desc, ffm_engine** out) {
     e->d.map = nullptr;
     e->d.sff = nullptr;
     e->HW = HW;
+    e->map0.resize((size_t)HW);
+    for (int i = 0; i < HW; i++) e->map0[(size_t)i] = d.map[i] == 0 ? 0 : d.map[i] == 3 ? 3 : 2;
     e->F = (int)fl.size();
     e->reset_thr = placement_threshold(d.n_agents, e->F, &e->reset_m);
     e->f64 = d.sff_dtype == FFM_SFF_F64;
@@ -700,15 +734,53 @@ static hipError_t launch_observer(const ffm_engine* e, const ffm::CoreStepArgs& 
     return ffm::launch_core_observe(o, e->fs_lds, e->fs_blocks, s);
 }
 
+// The exit flow's kernel (core_flow.hip) after the step launch `a` describes: that launch's envs
+// (e0: its first env, for the class array and the snapshot), its step index, its stream.
+static hipError_t launch_flow(const ffm_engine* e, const ffm::CoreStepArgs& a, long long e0, hipStream_t s) {
+    ffm::FlowArgs f{};
+    f.pos = a.pos;
+    f.cnt = a.cnt;
+    f.ep_start = a.ep_start;
+    f.prev_pos = e->d_prev_pos + e0 * a.A;
+    f.prev_cnt = e->d_prev_cnt + e0;
+    f.prev_start = e->d_prev_start + e0;
+    f.cls = e->d_xf_cls ? e->d_xf_cls + e0 : nullptr;
+    f.room_of_env = a.room_of_env;
+    f.door_from = e->d_xf_door_from;
+    f.tab = e->d_xf_tab;
+    f.E = a.E;
+    f.A = a.A;
+    f.HW = a.HW;
+    f.R = e->xf_rooms;
+    f.bins = e->xf_bins;
+    f.C = e->xf_classes;
+    f.D = e->xf_doors;
+    f.slots = e->xf_slots;
+    f.t = a.t;
+    return ffm::launch_core_flow(f, e->xf_lds, e->xf_blocks, s);
+}
+
+// The exit flow's snapshot invariant: whoever writes pos, cnt or ep_start ends with this, on the
+// same stream (the flow kernel carries the snapshot forward itself).  Whole arrays: the envs a
+// call left alone hold equal data already.  Nothing while the feature is off.
+static hipError_t refresh_flow_snapshot(ffm_engine* e, hipStream_t s) {
+    if (!exit_flow_on(e)) return hipSuccess;
+    const size_t Ep = ((size_t)e->d.n_envs + 7) & ~(size_t)7;
+    hipError_t he = hipMemcpyAsync(e->d_prev_pos, e->d_pos, Ep * e->d.agent_capacity * 2, hipMemcpyDeviceToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(e->d_prev_cnt, e->d_cnt, Ep * 4, hipMemcpyDeviceToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(e->d_prev_start, e->d_ep_start, Ep * 4, hipMemcpyDeviceToDevice, s);
+    return he;
+}
+
 // Shards a step(n > 1) call runs as, under the engine's current settings: 1 (one launch per
 // step over all envs) with trajectory capture on (its kernel follows every step launch on the
 // caller's stream), on the fused multi-step path and with per-env parameters on the lane kernel
 // (only plans of the group kernel hold shards; its per-env and room forms hold their own).
-// Field statistics keep the shards (the observer follows each shard's launch on that shard's
-// stream) and keep the engine off the fused path.
+// Field statistics and the exit flow keep the shards (their kernels follow each shard's launch on
+// that shard's stream) and keep the engine off the fused path.
 static int shards_in_effect(const ffm_engine* e) {
     const size_t S = plan(e).shards.size();
-    if (S <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi && !rooms_on(e) && !field_stats_on(e))) return 1;
+    if (S <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi && !rooms_on(e) && !observers_on(e))) return 1;
     return (int)S;
 }
 
@@ -746,6 +818,7 @@ static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
             he = ffm::launch_core_group(a, e->d.neighborhood, sh.blocks, k ? e->sh_stream[k - 1] : s, sh.g, p.one);
             // the shards add to the same slot copies: every add to them is an atomic
             if (he == hipSuccess && field_stats_on(e)) he = launch_observer(e, a, sh.e0, k ? e->sh_stream[k - 1] : s);
+            if (he == hipSuccess && exit_flow_on(e)) he = launch_flow(e, a, sh.e0, k ? e->sh_stream[k - 1] : s);
         }
     }
     // the join also after a failed launch: what was enqueued stays ordered before the caller's next work
@@ -764,7 +837,7 @@ static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
 int ffm_engine_step(ffm_engine* e, int32_t n_steps, void* stream) {
     if (!e || n_steps < 0) return fail(FFM_E_INVALID, "bad engine/n_steps");
     hipStream_t s = (hipStream_t)stream;
-    if (e->fused > 1 && e->multi && e->cap.n_sel == 0 && !rooms_on(e) && !field_stats_on(e)) {
+    if (e->fused > 1 && e->multi && e->cap.n_sel == 0 && !rooms_on(e) && !observers_on(e)) {
         // k steps per launch, the state of each env pair on chip (core_multi.hip)
         for (int done = 0; done < n_steps;) {
             const int k = std::min(e->fused, n_steps - done);
@@ -796,6 +869,7 @@ int ffm_engine_step(ffm_engine* e, int32_t n_steps, void* stream) {
         }
         if (e->cap.n_sel) HIP_TRY(ffm::launch_core_capture(a, e->cap, s));
         if (field_stats_on(e)) HIP_TRY(launch_observer(e, a, 0, s));
+        if (exit_flow_on(e)) HIP_TRY(launch_flow(e, a, 0, s));
         e->t++;
     }
     return FFM_OK;
@@ -829,6 +903,7 @@ int ffm_engine_reset(ffm_engine* e, void* stream) {
     }
     e->t++;
     if (e->cap.n_sel) HIP_TRY(ffm::launch_core_capture_init(make_args(e), e->cap, s));
+    HIP_TRY(refresh_flow_snapshot(e, s));
     return FFM_OK;
 }
 
@@ -849,6 +924,7 @@ int ffm_engine_reset_envs(ffm_engine* e, const uint8_t* mask, void* stream) {
     // trajectory capture: the masked envs' rows count from this placement (same episode index),
     // and one that had emptied logs again; nothing is launched while capture is off
     if (e->cap.n_sel) HIP_TRY(ffm::launch_core_capture_init(make_args(e), e->cap, s, mask));
+    HIP_TRY(refresh_flow_snapshot(e, s));
     return FFM_OK;
 }
 
@@ -908,6 +984,7 @@ int ffm_engine_set_state(ffm_engine* e, int64_t env0, int64_t n, const uint16_t*
     if (counts) HIP_TRY(hipMemcpyAsync(e->d_cnt + env0, counts, (size_t)n * 4, hipMemcpyHostToDevice, s));
     if (dff)
         HIP_TRY(hipMemcpyAsync(e->d_dff + env0 * e->HW, dff, (size_t)n * e->HW * 4, hipMemcpyHostToDevice, s));
+    if (positions || counts) HIP_TRY(refresh_flow_snapshot(e, s));
     HIP_TRY(hipStreamSynchronize(s));
     return FFM_OK;
 }
@@ -1243,6 +1320,195 @@ int ffm_debug_field_stats_info(ffm_engine* e, int32_t* out, int n) {
     return FFM_OK;
 }
 
+// The exit cells of room r's map in row-major order numbered 0, 1, ...: the default door labels.
+// Returns the room's exit count.
+static int default_doors(const uint8_t* map, int HW, int32_t* door_of_cell) {
+    int n = 0;
+    for (int i = 0; i < HW; i++) door_of_cell[i] = map[i] == 3 ? n++ : -1;
+    return n;
+}
+
+// door_from of one room (kernels.h FlowArgs): for every free cell the door of the first exit cell
+// among its neighbours in the reference's neighbour order (model/ffm_core.py:28-34: Neumann up,
+// down, left, right; Moore row-major), 0xFF for none.
+static void build_door_from(const uint8_t* map, const int32_t* door_of_cell, int H, int W, int nb, uint8_t* out) {
+    static const int dx4[4] = {-1, 1, 0, 0}, dy4[4] = {0, 0, -1, 1};
+    static const int dx8[8] = {-1, -1, -1, 0, 0, 1, 1, 1}, dy8[8] = {-1, 0, 1, -1, 1, -1, 0, 1};
+    const int* dx = nb == 4 ? dx4 : dx8;
+    const int* dy = nb == 4 ? dy4 : dy8;
+    for (int x = 0; x < H; x++)
+        for (int y = 0; y < W; y++) {
+            uint8_t d = 0xFF;
+            if (map[x * W + y] == 0)
+                for (int k = 0; k < nb && d == 0xFF; k++) {
+                    const int u = x + dx[k], v = y + dy[k];
+                    if (u >= 0 && u < H && v >= 0 && v < W && map[u * W + v] == 3) d = (uint8_t)door_of_cell[u * W + v];
+                }
+            out[x * W + y] = d;
+        }
+}
+
+int ffm_engine_set_exit_flow(ffm_engine* e, const int32_t* door_of_cell, int32_t n_doors, const int32_t* class_of_env,
+                             int32_t n_classes, int32_t curve_bins, void* stream) {
+    if (!e) return fail(FFM_E_INVALID, "null engine");
+    if (e->mt) return fail(FFM_E_UNSUPPORTED, "exit flow: Philox engines only");
+    if (n_classes < 0 || curve_bins < 0 || n_doors < 0) return fail(FFM_E_INVALID, "exit flow: negative class, door or bin count");
+    hipStream_t s = (hipStream_t)stream;
+    if (n_classes == 0) {
+        HIP_TRY(hipStreamSynchronize(s));    // queued flow kernels may still write the tables
+        free_exit_flow(e);
+        if (!e->d_eplog && !e->d_ephist) free_episode_log(e, true);   // ep_start, unless the field statistics need it
+        return FFM_OK;
+    }
+    const size_t E = (size_t)e->d.n_envs;
+    const int HW = e->HW, A = e->d.agent_capacity;
+    if (class_of_env)
+        for (size_t i = 0; i < E; i++)
+            if (class_of_env[i] < 0 || class_of_env[i] >= n_classes)
+                return fail(FFM_E_INVALID, "exit flow: class_of_env entry outside [0, n_classes)");
+    // the doors of every room in effect
+    const int R = rooms_on(e) ? (int)e->room_f.size() : 1;
+    const uint8_t* maps = rooms_on(e) ? e->room_maps.data() : e->map0.data();
+    std::vector<int32_t> doc((size_t)R * HW);
+    int D = 0;
+    for (int r = 0; r < R; r++) D = std::max(D, default_doors(maps + (size_t)r * HW, HW, doc.data() + (size_t)r * HW));
+    if (door_of_cell) {
+        if (n_doors < 1) return fail(FFM_E_INVALID, "exit flow: door_of_cell wants n_doors >= 1");
+        for (size_t i = 0; i < doc.size(); i++) {
+            if (doc[i] < 0) continue;            // only exit cells are read
+            if (door_of_cell[i] < 0 || door_of_cell[i] >= n_doors)
+                return fail(FFM_E_INVALID, "exit flow: an exit cell's door label outside [0, n_doors)");
+            doc[i] = door_of_cell[i];
+        }
+        D = n_doors;
+    }
+    D = std::max(D, 1);
+    if (D > 255) return fail(FFM_E_INVALID, "exit flow: more than 255 doors");
+    // one copy of the tables as u64, against FFM_EXIT_FLOW_MAX_BYTES
+    const size_t words = (size_t)n_classes * D * (1 + (size_t)curve_bins);
+    if (words * 8 > (size_t)FFM_EXIT_FLOW_MAX_BYTES)
+        return fail(FFM_E_INVALID, "exit flow: n_classes * doors * (1 + curve_bins) * 8 exceeds FFM_EXIT_FLOW_MAX_BYTES");
+    // The form.  FFM_EXIT_FLOW_FORM=lds|global forces one, FFM_EXIT_FLOW_BLOCKS caps the grid (A/B
+    // and test switches, read here).
+    const int blocks = fs_env_int("FFM_EXIT_FLOW_BLOCKS", ffm::kFlowMaxBlocks, 1, 65535);
+    const bool fits = words * 4 <= ffm::kObserveLdsBudget && ffm::core_flow_lds_safe(e->d.n_envs, A);
+    bool lds = fits;
+    if (const char* ov = std::getenv("FFM_EXIT_FLOW_FORM")) {
+        if (!std::strcmp(ov, "lds")) {
+            if (!fits) return fail(FFM_E_INVALID, "exit flow: FFM_EXIT_FLOW_FORM=lds, but the tables exceed the LDS budget");
+            lds = true;
+        } else if (!std::strcmp(ov, "global")) {
+            lds = false;
+        }
+    }
+    int slots = ffm::kFlowSlots;   // a power of two, fewer where the copies together would pass the limit
+    while (slots > 1 && words * 8 * (size_t)slots > (size_t)FFM_EXIT_FLOW_MAX_BYTES) slots /= 2;
+    std::vector<uint8_t> dfrom((size_t)R * HW);
+    for (int r = 0; r < R; r++)
+        build_door_from(maps + (size_t)r * HW, doc.data() + (size_t)r * HW, e->d.H, e->d.W, e->d.neighborhood,
+                        dfrom.data() + (size_t)r * HW);
+
+    HIP_TRY(hipStreamSynchronize(s));        // queued flow kernels may still write the old tables
+    // Build into locals; the engine changes after the last call that can fail.
+    unsigned long long* tab = nullptr;
+    int32_t* cls = nullptr;
+    uint8_t* d_dfrom = nullptr;
+    uint16_t* ppos = nullptr;
+    int32_t* pcnt = nullptr;
+    uint32_t* pstart = nullptr;
+    uint32_t* ep_start = nullptr;
+    const bool fresh = e->d_ep_start == nullptr;
+    const size_t Ep = (E + 7) & ~(size_t)7;   // padded like d_cnt
+    hipError_t he = hipMalloc((void**)&tab, words * 8 * (size_t)slots);
+    if (he == hipSuccess && class_of_env) he = hipMalloc((void**)&cls, E * 4);
+    if (he == hipSuccess) he = hipMalloc((void**)&d_dfrom, dfrom.size());
+    if (he == hipSuccess) he = hipMalloc((void**)&ppos, Ep * A * 2 + 512);   // sized like d_pos
+    if (he == hipSuccess) he = hipMalloc((void**)&pcnt, Ep * 4);
+    if (he == hipSuccess) he = hipMalloc((void**)&pstart, Ep * 4);
+    if (he == hipSuccess && fresh) he = hipMalloc((void**)&ep_start, Ep * 4);
+    const bool nomem = he != hipSuccess;
+    if (he == hipSuccess) he = hipMemsetAsync(tab, 0, words * 8 * (size_t)slots, s);
+    if (he == hipSuccess && cls) he = hipMemcpyAsync(cls, class_of_env, E * 4, hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(d_dfrom, dfrom.data(), dfrom.size(), hipMemcpyHostToDevice, s);
+    // Turned on mid-run: episodes in flight count from here, as the episode log's do (the next
+    // step is keyed e->t, so the index that "placed" every env is the one before it).
+    if (he == hipSuccess && fresh) he = hipMemsetD32Async((hipDeviceptr_t)ep_start, (int)(e->t - 1u), Ep, s);
+    // the snapshot: the state as it stands
+    if (he == hipSuccess) he = hipMemcpyAsync(ppos, e->d_pos, Ep * A * 2, hipMemcpyDeviceToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(pcnt, e->d_cnt, Ep * 4, hipMemcpyDeviceToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(pstart, fresh ? ep_start : e->d_ep_start, Ep * 4, hipMemcpyDeviceToDevice, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    if (he != hipSuccess) {
+        void* bufs[] = {tab, cls, d_dfrom, ppos, pcnt, pstart, ep_start};
+        for (void* p : bufs) (void)hipFree(p);
+        return fail(nomem ? FFM_E_NOMEM : FFM_E_HIP, std::string("exit flow: ") + hipGetErrorString(he));
+    }
+    free_exit_flow(e);
+    e->d_xf_tab = tab;
+    e->d_xf_cls = cls;
+    e->d_xf_door_from = d_dfrom;
+    e->d_prev_pos = ppos;
+    e->d_prev_cnt = pcnt;
+    e->d_prev_start = pstart;
+    if (fresh) e->d_ep_start = ep_start;
+    e->xf_classes = n_classes;
+    e->xf_doors = D;
+    e->xf_bins = curve_bins;
+    e->xf_slots = slots;
+    e->xf_blocks = blocks;
+    e->xf_rooms = R;
+    e->xf_lds = lds;
+    e->xf_door_of_cell = std::move(doc);
+    return FFM_OK;
+}
+
+int ffm_engine_get_exit_flow(ffm_engine* e, uint64_t* exited, uint64_t* outflow, int32_t clear, void* stream) {
+    if (!e) return fail(FFM_E_INVALID, "null engine");
+    if (!exit_flow_on(e)) return fail(FFM_E_INVALID, "the exit flow is off");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t words = xf_words(e), bins = (size_t)e->xf_bins, CD = (size_t)e->xf_classes * e->xf_doors;
+    std::vector<unsigned long long> h(words * (size_t)e->xf_slots);
+    HIP_TRY(hipMemcpyAsync(h.data(), e->d_xf_tab, h.size() * 8, hipMemcpyDeviceToHost, s));
+    if (clear) HIP_TRY(hipMemsetAsync(e->d_xf_tab, 0, h.size() * 8, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int k = 1; k < e->xf_slots; k++)
+        for (size_t i = 0; i < words; i++) h[i] += h[(size_t)k * words + i];
+    for (size_t cd = 0; cd < CD; cd++) {
+        const unsigned long long* T = h.data() + cd * (1 + bins);
+        if (exited) exited[cd] = T[0];
+        if (outflow) std::copy(T + 1, T + 1 + bins, outflow + cd * bins);
+    }
+    return FFM_OK;
+}
+
+int ffm_engine_get_exit_doors(ffm_engine* e, int32_t* door_of_cell, int32_t* n_doors) {
+    if (!e) return fail(FFM_E_INVALID, "null engine");
+    if (!exit_flow_on(e)) return fail(FFM_E_INVALID, "the exit flow is off");
+    if (door_of_cell) std::copy(e->xf_door_of_cell.begin(), e->xf_door_of_cell.end(), door_of_cell);
+    if (n_doors) *n_doors = e->xf_doors;
+    return FFM_OK;
+}
+
+// Diagnostic (not part of the ABI header): the exit flow in effect.
+//   out[0] 0 off, 1 the LDS form, 2 the global form;  out[1] blocks of the flow kernel's grid over
+//   all envs;  out[2] slot copies of the tables;  out[3] classes;  out[4] doors;  out[5] curve bins;
+//   out[6] rooms of the door table
+int ffm_debug_exit_flow_info(ffm_engine* e, int32_t* out, int n) {
+    if (!e || !out || n < 0 || n > 7) return fail(FFM_E_INVALID, "bad args");
+    const bool on = exit_flow_on(e);
+    const int32_t v[7] = {
+        !on ? 0 : e->xf_lds ? 1 : 2,
+        on ? ffm::core_flow_grid(e->d.n_envs, e->d.agent_capacity, e->xf_blocks) : 0,
+        e->xf_slots,
+        e->xf_classes,
+        e->xf_doors,
+        e->xf_bins,
+        e->xf_rooms,
+    };
+    for (int i = 0; i < n; i++) out[i] = v[i];
+    return FFM_OK;
+}
+
 // One env's record (kernels.h EnvParams) from its parameter set, with the expressions of
 // ffm_engine_create (the same bits as a homogeneous engine).  F: the free cells of the env's room.
 static ffm::EnvParams env_record(const ffm_env_params& q, int nb, int F) {
@@ -1447,6 +1713,8 @@ int ffm_engine_get_env_params(ffm_engine* e, ffm_env_params* sets, int32_t cap, 
 int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sffs, int32_t n_rooms,
                              const int32_t* room_of_env, void* stream) {
     if (!e) return fail(FFM_E_INVALID, "null engine");
+    // the door table is built from the rooms in effect when the flow is set: rooms first, the flow after
+    if (exit_flow_on(e)) return fail(FFM_E_INVALID, "env rooms: the exit flow is on (turn it off, set the rooms, set it again)");
     hipStream_t s = (hipStream_t)stream;
     const size_t E = (size_t)e->d.n_envs;
     const bool pep = pep_on(e);

@@ -158,6 +158,35 @@ int core_observe_grid(long long E, int run, int max_blocks);
 bool core_observe_lds_safe(long long E, int A, int run, int max_blocks);
 hipError_t launch_core_observe(const ObserveArgs& o, bool lds, int max_blocks, hipStream_t s);
 
+// Exit flow (ffm_engine_set_exit_flow; core_flow.hip): what the flow kernel launched after a step
+// launch reads -- that launch's slices of pos, cnt, ep_start, the class array and the room indices,
+// the snapshot of the same envs before the step (prev_*) and the door table -- and the tables it
+// adds to.  One (class, door) record is 1 + bins words: exited, outflow[bins]; `tab` holds `slots`
+// (a power of two) copies of the C * D records, summed by the host when it reads.  The kernel ends
+// by storing pos, cnt and ep_start into prev_*: whoever else writes one of the three refreshes the
+// snapshot on the same stream (engine.cpp refresh_flow_snapshot).
+struct FlowArgs {
+    const uint16_t* pos;           // [E][A] after the step
+    const int* cnt;                // [E]
+    const uint32_t* ep_start;      // [E]
+    uint16_t* prev_pos;            // [E][A] before the step; after the kernel: pos
+    int* prev_cnt;                 // [E]
+    uint32_t* prev_start;          // [E]
+    const int* cls;                // [E] class of every env, or nullptr (class 0)
+    const int* room_of_env;        // [E] or nullptr (room 0)
+    const uint8_t* door_from;      // [R][HW] door id of the first exit among a cell's neighbours, 0xFF: none
+    unsigned long long* tab;       // [slots][C][D][1 + bins]
+    long long E;
+    int A, HW, R, bins, C, D, slots;
+    uint32_t t;                    // the step index that keyed the step launch
+};
+// The flow kernel's LDS budget is the observer's; its slot copies and largest grid
+// (FFM_EXIT_FLOW_BLOCKS overrides the grid when the feature is set; profiles/exit_flow/).
+constexpr int kFlowSlots = 16, kFlowMaxBlocks = 1024;
+int core_flow_grid(long long E, int A, int max_blocks);
+bool core_flow_lds_safe(long long E, int A);
+hipError_t launch_core_flow(const FlowArgs& f, bool lds, int max_blocks, hipStream_t s);
+
 size_t core_wave_smem_bytes(int H, int W, int A, int F, bool mt, bool reset, int waves);
 size_t core_block_smem_bytes(int H, int W, int A, int K, int F, bool f64, bool mt, bool reset);
 hipError_t launch_core_wave(const CoreStepArgs& a, int nb, bool mt, int blocks, hipStream_t s);

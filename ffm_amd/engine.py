@@ -31,6 +31,7 @@ EXPORTED = [
     "ffm_engine_set_trajectory_capture", "ffm_engine_drain_trajectory",
     "ffm_engine_set_episode_log", "ffm_engine_drain_episodes", "ffm_engine_get_episode_stats",
     "ffm_engine_set_field_stats", "ffm_engine_get_field_stats",
+    "ffm_engine_set_exit_flow", "ffm_engine_get_exit_flow", "ffm_engine_get_exit_doors",
     "ffm_debug_stage_image", "ffm_debug_reset_candidates",
     "ffm_engine_set_env_params", "ffm_engine_get_env_params", "ffm_engine_set_env_params_kernel",
     "ffm_engine_set_env_rooms", "ffm_engine_get_env_rooms", "ffm_engine_set_env_rooms_kernel",
@@ -153,6 +154,9 @@ def load_library():
     L.ffm_engine_get_episode_stats.argtypes = [P, P, i32, P, i32, P]
     L.ffm_engine_set_field_stats.argtypes = [P, P, i32, i32, P]
     L.ffm_engine_get_field_stats.argtypes = [P, P, P, P, P, i32, P]
+    L.ffm_engine_set_exit_flow.argtypes = [P, P, i32, P, i32, i32, P]
+    L.ffm_engine_get_exit_flow.argtypes = [P, P, P, i32, P]
+    L.ffm_engine_get_exit_doors.argtypes = [P, P, C.POINTER(i32)]
     L.ffm_engine_set_env_params.argtypes = [P, C.POINTER(EnvParams), i32, P, P]
     L.ffm_engine_get_env_params.argtypes = [P, C.POINTER(EnvParams), i32, C.POINTER(i32), P]
     L.ffm_engine_set_env_params_kernel.argtypes = [P, i32]
@@ -653,6 +657,57 @@ class Engine:
                                                   int(bool(clear)), _stream_handle(stream)))
         return {"occupancy": occ, "observed": obs, "remaining": rem, "alive": alive}
 
+    # -- exit flow ---------------------------------------------------------------
+    def _exit_flow_info(self) -> np.ndarray:
+        # bound here, as group_occupancy()'s: a diagnostic outside the ABI header
+        v = np.zeros(7, np.int32)
+        fn = self._L.ffm_debug_exit_flow_info
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_int], C.c_int
+        _check(fn(self._h, _ptr(v), len(v)))
+        return v
+
+    def set_exit_flow(self, doors=None, classes=None, n_classes: int | None = None, curve_bins: int = 0, stream=None):
+        """Count, on the device and per class of envs, which exit cell ("door") the agents leave
+        through and when (the reference decides the door in model/ffm_core.py:66-72, 100-102); see
+        ffm_engine_set_exit_flow.  `doors`: None numbers every room's exit cells in row-major order;
+        else door labels [R, H, W] ([H, W] for one room), read at the exit cells only, with
+        max(doors) + 1 doors (give -1 or 0 off the exits) -- a 4-wide exit can be one door.
+        `classes` / `n_classes` as set_field_stats (0 = off); `curve_bins` > 0 adds `outflow` over the
+        steps since placement (the last bin holds every later step).  Set the rooms first
+        (set_env_rooms raises ValueError while the flow is on).  While on, step(n) takes one launch
+        per step (no fused steps) and a flow launch follows each; read with exit_flow()."""
+        cls = None
+        if classes is not None:
+            cls = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1)
+            if cls.size != self.n_envs:
+                raise ValueError(f"classes must have n_envs = {self.n_envs} entries, got {cls.size}")
+        if n_classes is None:
+            n_classes = 1 if cls is None else int(cls.max()) + 1
+        doc, n_doors = None, 0
+        if doors is not None and int(n_classes) != 0:
+            doc = np.ascontiguousarray(doors, dtype=np.int32)
+            rooms = max(1, self.launch_info()["env_rooms"])
+            if doc.size != rooms * self.H * self.W:
+                raise ValueError(f"doors must be [{rooms}, {self.H}, {self.W}], got {doc.shape}")
+            n_doors = max(1, int(doc.max()) + 1)
+        _check(self._L.ffm_engine_set_exit_flow(self._h, _ptr(doc), int(n_doors), _ptr(cls), int(n_classes),
+                                                int(curve_bins), _stream_handle(stream)))
+
+    def exit_flow(self, clear: bool = False, stream=None) -> dict:
+        """The exit flow: exited [C, D] and outflow [C, D, bins] (uint64; outflow is empty without
+        curve_bins) and door_of_cell [R, H, W] int32, the door of every exit cell of every room, -1
+        off the exits.  outflow[c, d, tau] over the number of episodes is door d's mean flow tau
+        steps after placement.  clear=True zeroes the counts after the read."""
+        v = self._exit_flow_info()
+        c, d, bins, rooms = (int(v[3]), int(v[4]), int(v[5]), int(v[6])) if v[0] else (0, 0, 0, 0)
+        exited = np.zeros((c, d), np.uint64)
+        outflow = np.zeros((c, d, bins), np.uint64)
+        doc = np.zeros((rooms, self.H, self.W), np.int32)
+        _check(self._L.ffm_engine_get_exit_flow(self._h, _ptr(exited), _ptr(outflow), int(bool(clear)),
+                                                _stream_handle(stream)))
+        _check(self._L.ffm_engine_get_exit_doors(self._h, _ptr(doc), None))
+        return {"exited": exited, "outflow": outflow, "door_of_cell": doc}
+
     def run_episodes(self, per_env: int = 1, max_steps: int | None = None, chunk: int = 16, stream=None) -> np.ndarray:
         """Step until every env has logged `per_env` episodes and return their lengths, int32
         [E, per_env] indexed by episode (counted from the last reset()): E replicas of
@@ -793,7 +848,9 @@ class Engine:
         "group_one" True, with that form's own blocks and shards).
         "field_stats": "off", or with set_field_stats() on a dict of the observer's form ("lds" or
         "global"), its grid's blocks over all envs, the tables' slot copies, the classes and the
-        curve bins."""
+        curve bins.
+        "exit_flow": "off", or with set_exit_flow() on a dict of the flow kernel's form, its grid's
+        blocks over all envs, the tables' slot copies, the classes, the doors and the curve bins."""
         v = np.zeros(10, np.int32)
         _check(self._L.ffm_debug_launch_info(self._h, _ptr(v), len(v)))
         rooms = C.c_int32()
@@ -805,7 +862,11 @@ class Engine:
         _check(fn(self._h, _ptr(fs), len(fs)))
         field_stats = "off" if fs[0] == 0 else {"form": ("lds", "global")[int(fs[0]) - 1], "blocks": int(fs[1]),
                                                 "slots": int(fs[2]), "classes": int(fs[3]), "curve_bins": int(fs[4])}
-        return {"env_rooms": int(rooms.value), "field_stats": field_stats,
+        xf = self._exit_flow_info()
+        exit_flow = "off" if xf[0] == 0 else {"form": ("lds", "global")[int(xf[0]) - 1], "blocks": int(xf[1]),
+                                              "slots": int(xf[2]), "classes": int(xf[3]), "doors": int(xf[4]),
+                                              "curve_bins": int(xf[5])}
+        return {"env_rooms": int(rooms.value), "field_stats": field_stats, "exit_flow": exit_flow,
                 "kernel": ("group", "lane", "wave", "block", "block_scratch")[int(v[0])], "group_g": int(v[1]),
                 "blocks": int(v[2]), "K": int(v[3]), "block_size": int(v[4]), "multi": bool(v[5]),
                 "multi_blocks": int(v[6]), "step_shards": int(v[7]), "shard_blocks": int(v[8]),

@@ -55,6 +55,15 @@ With ``--episodes`` > 1 an env that finishes early keeps evacuating until the sl
 those episodes are observed too: normalise by ``observed`` and ``alive``, not by ``--episodes``.
 
     python -m ffm_amd.evac --room 12 12 --sweep exit_width=1,2,4 --fields --curve-bins 128 --envs 4096 --out runs/fields
+
+``--flow`` adds which exit the agents leave through and when (``model/ffm_core.py:66-72, 100-102``
+decides the door), counted on the device (``Engine.set_exit_flow``) with one class per sweep
+combination: every exit cell of every room is a door, numbered in row-major order within its room.
+It writes ``exit_usage.csv`` (``set,door,exited``), ``doors.csv`` (``room,door,row,col``: where each
+door is) and, with ``--curve-bins B``, ``outflow.csv`` (``set,door,tau,exited``: the agents that left
+through the door tau steps after placement; the last tau holds every later step too).
+
+    python -m ffm_amd.evac --room 12 12 --sweep exit_width=1,2,4 --flow --curve-bins 128 --envs 4096 --out runs/flow
 """
 from __future__ import annotations
 
@@ -248,6 +257,46 @@ def remaining_csv(remaining, alive) -> str:
     return "\n".join(lines) + "\n"
 
 
+def exit_usage_csv(exited) -> str:
+    """The text of exit_usage.csv from Engine.exit_flow()["exited"] [P, D]: ``set,door,exited`` for
+    every set and door, in that order (a door the set's room does not have reads 0)."""
+    ex = np.asarray(exited)
+    if ex.ndim != 2:
+        raise ValueError("exited is a [sets, doors] array")
+    lines = ["set,door,exited"]
+    for p in range(ex.shape[0]):
+        for d in range(ex.shape[1]):
+            lines.append(f"{p},{d},{int(ex[p, d])}")
+    return "\n".join(lines) + "\n"
+
+
+def doors_csv(door_of_cell) -> str:
+    """The text of doors.csv from Engine.exit_flow()["door_of_cell"] [R, H, W] (-1 off the exits):
+    ``room,door,row,col``, one row per exit cell in (room, row, col) order."""
+    doc = np.asarray(door_of_cell)
+    if doc.ndim != 3:
+        raise ValueError("door_of_cell is a [rooms, H, W] array")
+    lines = ["room,door,row,col"]
+    for r, x, y in np.argwhere(doc >= 0).tolist():
+        lines.append(f"{r},{int(doc[r, x, y])},{x},{y}")
+    return "\n".join(lines) + "\n"
+
+
+def outflow_csv(outflow) -> str:
+    """The text of outflow.csv from Engine.exit_flow()["outflow"] [P, D, bins]:
+    ``set,door,tau,exited`` for every set, door and tau = 0 .. bins - 1 (tau: steps since the
+    placement; the last holds every later step too; nobody leaves at tau = 0)."""
+    out = np.asarray(outflow)
+    if out.ndim != 3:
+        raise ValueError("outflow is a [sets, doors, bins] array")
+    lines = ["set,door,tau,exited"]
+    for p in range(out.shape[0]):
+        for d in range(out.shape[1]):
+            for tau in range(out.shape[2]):
+                lines.append(f"{p},{d},{tau},{int(out[p, d, tau])}")
+    return "\n".join(lines) + "\n"
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--map", help=".npy map (0 free, 2 wall, 3 exit)")
@@ -280,9 +329,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fields", action="store_true",
                     help="also write the on-device field statistics (Engine.set_field_stats), one class per sweep "
                          "combination: occupancy.npy, occupancy.csv, observed.csv")
+    ap.add_argument("--flow", action="store_true",
+                    help="also write the on-device exit flow (Engine.set_exit_flow), one class per sweep "
+                         "combination: exit_usage.csv, doors.csv")
     ap.add_argument("--curve-bins", type=int, default=0, metavar="B",
-                    help="with --fields: the evacuation curve over tau = 0 .. B - 1 steps since placement "
-                         "(remaining.csv)")
+                    help="with --fields or --flow: the curves over tau = 0 .. B - 1 steps since placement "
+                         "(remaining.csv, outflow.csv)")
     ap.add_argument("--out", required=True, metavar="DIR")
     return ap
 
@@ -290,8 +342,8 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
-    if a.curve_bins < 0 or (a.curve_bins and not a.fields):
-        ap.error("--curve-bins B wants B >= 0 and --fields")
+    if a.curve_bins < 0 or (a.curve_bins and not (a.fields or a.flow)):
+        ap.error("--curve-bins B wants B >= 0 and --fields or --flow")
     if sum(map(bool, (a.map, a.room, a.rooms))) != 1 or (a.rooms and a.sff):
         ap.error("give either --map and --sff, or --room H W, or --rooms MAP.npy:SFF.npy ...")
     try:
@@ -361,12 +413,15 @@ def main(argv=None):
     if a.fields:   # the class is the sweep's combination index
         eng.set_field_stats(classes=soe if sets else None, n_classes=len(sets) if sets else 1,
                             curve_bins=a.curve_bins)
+    if a.flow:     # after the rooms: the doors are those of the rooms in effect
+        eng.set_exit_flow(classes=soe if sets else None, n_classes=len(sets) if sets else 1, curve_bins=a.curve_bins)
     eng.reset()
     t0 = time.perf_counter()
     steps = eng.run_episodes(per_env=a.episodes, max_steps=a.max_steps)
     dt = time.perf_counter() - t0
     taken = eng.counters()["steps"]
     fields = eng.field_stats() if a.fields else None
+    flow = eng.exit_flow() if a.flow else None
     eng.close()
 
     os.makedirs(a.out, exist_ok=True)
@@ -375,6 +430,13 @@ def main(argv=None):
         texts = {"occupancy.csv": occupancy_csv(fields["occupancy"]), "observed.csv": observed_csv(fields["observed"])}
         if a.curve_bins > 0:
             texts["remaining.csv"] = remaining_csv(fields["remaining"], fields["alive"])
+        for name, body in texts.items():
+            with open(os.path.join(a.out, name), "w") as f:
+                f.write(body)
+    if flow is not None:
+        texts = {"exit_usage.csv": exit_usage_csv(flow["exited"]), "doors.csv": doors_csv(flow["door_of_cell"])}
+        if a.curve_bins > 0:
+            texts["outflow.csv"] = outflow_csv(flow["outflow"])
         for name, body in texts.items():
             with open(os.path.join(a.out, name), "w") as f:
                 f.write(body)

@@ -279,6 +279,59 @@ int ffm_engine_set_field_stats(ffm_engine* eng, const int32_t* class_of_env, int
 int ffm_engine_get_field_stats(ffm_engine* eng, uint64_t* occupancy, uint64_t* observed, uint64_t* remaining,
                                uint64_t* alive, int32_t clear, void* stream);
 
+/* Exit flow: which exit the agents leave through, and when, summed on the device.  The reference
+ * decides the door in model/ffm_core.py:66-72, 100-102: an agent with an exit among its free
+ * neighbours always requests the first exit in neighbour order, and whoever reaches an exit is
+ * dropped from `positions`.  That last move is invisible to ffm_engine_get_state (the agent is
+ * removed in the same step, and the step that empties an env re-places it); here a kernel follows
+ * every step launch, compares the positions before and after it, and nothing leaves the device.
+ *
+ * Doors.  Every exit cell of every room in effect (the create-time room, or the rooms of
+ * ffm_engine_set_env_rooms) has a door id in [0, D).  door_of_cell == NULL: a room's exit cells
+ * numbered in row-major order, D the largest count over the rooms (n_doors is ignored).  Else
+ * door_of_cell[R][H * W] with D = n_doors >= 1: only the entries of exit cells are read, each in
+ * [0, n_doors) -- a 4-wide exit can be one door.  D <= 255.
+ * Per class c (class_of_env / n_classes as for the field statistics) the engine keeps, as u64,
+ *   exited[c][d]           agents that left through door d
+ *   outflow[c][d][bins]    the same by time since placement   (bins = curve_bins > 0)
+ * After every step launch keyed t, for every env e of it and every agent that left in that step
+ * through door d: tau = t - ep_start_before[e] in wrapping u32 (ep_start as it was before the
+ * step: the auto-reset overwrites it), b = min(tau, bins - 1),
+ *   exited[c][d] += 1;  outflow[c][d][b] += 1.
+ * tau >= 1 always; the last agents of an episode are counted with the episode's length.  An agent
+ * left iff its cell before the step has a door (the first exit cell among the cell's neighbours in
+ * neighbour order) and is not among the positions after the step; a step that emptied the env
+ * took every agent.  Every sum is an integer: the same bits under any launch geometry, step
+ * shards, the fused-steps setting and either form of the kernel (FFM_EXIT_FLOW_FORM=lds|global
+ * forces one and FFM_EXIT_FLOW_BLOCKS caps its grid, both read by this call; lds on tables beyond
+ * the LDS budget: FFM_E_INVALID).  The step itself does not change.
+ *
+ * n_classes == 0 turns the feature off and frees everything.  FFM_E_INVALID, the engine exactly as
+ * it was: a negative count, a class outside [0, n_classes), an exit cell's label outside
+ * [0, n_doors), more than 255 doors, or tables of more than FFM_EXIT_FLOW_MAX_BYTES (one copy:
+ * n_classes * D * (1 + curve_bins) * 8 bytes).  Philox only (MT: FFM_E_UNSUPPORTED).  Setting it
+ * again replaces doors, classes and bins and clears.
+ *
+ * While on, the engine keeps a snapshot of positions, counts and ep_start (2 A + 8 bytes per env),
+ * ffm_engine_step takes one launch per step (no fused steps, as for the field statistics; the
+ * state is the same bits) and the flow kernel follows each, on each step shard's own stream where
+ * shards are in effect.  ffm_engine_reset, ffm_engine_reset_envs and ffm_engine_set_state refresh
+ * the snapshot on their stream; ffm_engine_reset clears nothing.  ep_start is shared with the
+ * episode log and the field statistics; turned on mid-run, episodes in flight count from the
+ * steps taken after the call.  Works with the log, trajectory capture and the field statistics
+ * on.  Rooms first, the flow after: ffm_engine_set_env_rooms (on or off) while the flow is on
+ * returns FFM_E_INVALID and leaves the engine as it was.  ffm_engine_set_step_index inside an
+ * episode leaves the affected tau undefined.  Synchronises the stream. */
+#define FFM_EXIT_FLOW_MAX_BYTES FFM_FIELD_STATS_MAX_BYTES
+int ffm_engine_set_exit_flow(ffm_engine* eng, const int32_t* door_of_cell, int32_t n_doors, const int32_t* class_of_env,
+                             int32_t n_classes, int32_t curve_bins, void* stream);
+/* exited[C][D] and outflow[C][D][bins] to the host (either may be NULL).  clear != 0 zeroes them
+ * afterwards.  Feature off: FFM_E_INVALID.  Synchronises the stream. */
+int ffm_engine_get_exit_flow(ffm_engine* eng, uint64_t* exited, uint64_t* outflow, int32_t clear, void* stream);
+/* The door labels in effect: door_of_cell[R][H * W] (-1 off the exits; R = 1 without per-env
+ * rooms) and *n_doors = D (either may be NULL).  Feature off: FFM_E_INVALID. */
+int ffm_engine_get_exit_doors(ffm_engine* eng, int32_t* door_of_cell, int32_t* n_doors);
+
 /* Per-env parameters and agent counts: a whole sweep in one engine.  Replaces the user's loop
  * over FloorFieldModel(params=...) instances, one per point of an evacuation-time-against-N
  * curve (analyze_steps_by_n.py) or of the (k_S, k_D) plane -- each far too small to fill the

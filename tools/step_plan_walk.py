@@ -121,6 +121,7 @@ def _state(eng):
     import torch
     info = eng.launch_info()
     info.pop("field_stats", None)    # the observer's settings are no part of a step plan (off throughout the walk)
+    info.pop("exit_flow", None)      # nor are the exit flow's
     rec = {"launch_info": info, "occupancy_one": eng.group_occupancy(True), "occupancy_loop": eng.group_occupancy(False),
            "counter_slots": int(eng.device_buffers()["counter_slots"]), "sets": len(eng.env_params()[0]),
            "rooms": info["env_rooms"]}
