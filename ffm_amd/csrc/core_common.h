@@ -65,6 +65,27 @@ __device__ __forceinline__ T np_sum(const T (&e)[NB + 1], const bool (&v)[NB + 1
     return res;
 }
 
+// model/ffm_core.py:82, `if np.isfinite(probs_sum) and probs_sum != 0:` -- when it fails the agent
+// makes no request: no draw, no entry in move_requests, no DFF increment.  The sum fails it
+// exactly when a valid candidate's score minus the maximum is NaN (every candidate -inf, one
+// +inf, or a NaN score: an inf SFF on a passable cell, k_S = 0 times inf, k_D * DFF overflowing
+// float32); otherwise the maximum's own term is 1 and the sum lies in [1, 9].  The fast passes
+// need no such test: a NaN term makes their total NaN, every comparison with it false, and the
+// agent falls to the exact pass (kPending), which tests the sum here.
+// The lane and group kernels' exact passes apply the test to the total of the float64 cdf, a
+// value they hold to their end anyway, instead of the sum: it fails the test exactly when the
+// sum does.  A NaN sum makes every p = e / sum NaN; an infinite one makes every p 0 or NaN; a
+// zero one means every e is 0, and 0 / 0 is NaN; so the total is then NaN or 0.  A finite
+// non-zero sum gives a total near 1.
+#ifndef FFM_NOREQ_MUTATE
+#define FFM_NOREQ_MUTATE 0   // diagnostic builds only: 1 leaves the test out (profiles/no_request/)
+#endif
+template <class T>
+__device__ __forceinline__ bool no_request_sum(T sum) {
+    if (FFM_NOREQ_MUTATE) return false;
+    return !(__builtin_isfinite(sum) && sum != T(0));
+}
+
 // np.random.choice's comparison fl(cdf_k / cdf_last) > u without a float64
 // division in the common case: q = cdf_k * (1/cdf_last) is within a few ulp
 // of the correctly rounded quotient, so it decides unless it lands within
@@ -187,7 +208,15 @@ __device__ __forceinline__ uint32_t decide(int pp, int PW, const GT* grid, const
         const double u = draw.get();                                 // :84
         if (nvalid == 0) return kNoReq;                              // :63
         if (exit_slot >= 0) return (uint32_t)exit_slot;
-        if (u < 0.0) return kPending;
+        if (u < 0.0) {
+            // MT pass 1 (no draw yet): :82 is decided here, before the draw pass hands out the
+            // stream's draws in agent order -- an agent without a request takes none.  The sum
+            // is NaN exactly when an argument is (no_request_sum); invalid slots hold -inf.
+            bool nan_arg = false;
+#pragma unroll
+            for (int k = 0; k <= NB; k++) nan_arg = nan_arg || xs[k] != xs[k];
+            return (nan_arg && !FFM_NOREQ_MUTATE) ? kNoReq : kPending;
+        }
         const int fs = fast_choice<NB>(xs, v, u);
         if (fs >= 0) return (uint32_t)fs;
         // u is within the margin of a boundary: the exact NumPy arithmetic decides.
@@ -195,6 +224,7 @@ __device__ __forceinline__ uint32_t decide(int pp, int PW, const GT* grid, const
 #pragma unroll
         for (int k = 0; k <= NB; k++) e[k] = v[k] ? np_expf(xs[k]) : 0.0f;                // :80
         const float sum = np_sum<NB, float>(e, v, nc);                                    // :81
+        if (no_request_sum(sum)) return kNoReq;                                           // :82
         double cdf[NB + 1];
         double acc = 0.0;
 #pragma unroll
@@ -218,6 +248,7 @@ __device__ __forceinline__ uint32_t decide(int pp, int PW, const GT* grid, const
 #pragma unroll
         for (int k = 0; k <= NB; k++) e[k] = v[k] ? exp(sc[k] - mx) : 0.0;
         const double sum = np_sum<NB, double>(e, v, nc);
+        if (no_request_sum(sum)) return kNoReq;                      // :82, before the draw (MT: none is taken)
         double cdf[NB + 1];
         double acc = 0.0;
 #pragma unroll

@@ -246,7 +246,8 @@ __device__ __forceinline__ uint32_t group_exact_coop(unsigned long long pend, ui
         const double u = u53((uint32_t)__builtin_amdgcn_readlane((int)wx, L),
                              (uint32_t)__builtin_amdgcn_readlane((int)wy, L));
         const unsigned gt = (unsigned)__ballot(cdf_gt(run, last, inv, u)) & vm & ((1u << NB) - 1u);
-        const uint32_t pick = gt ? (uint32_t)__builtin_ctz(gt) : (uint32_t)NB;         // cdf[-1] == 1 > u
+        const uint32_t pick = no_request_sum(last) ? (uint32_t)kNoReq                  // :82 (wave-uniform)
+                              : gt ? (uint32_t)__builtin_ctz(gt) : (uint32_t)NB;       // cdf[-1] == 1 > u
         slot = lane == L ? pick : slot;
     }
     return slot;

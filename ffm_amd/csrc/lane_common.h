@@ -159,8 +159,9 @@ __device__ __forceinline__ uint32_t lane_decide(int pp, int PW, const uint16_t* 
            : cs > t + d ? (uint32_t)slot : (uint32_t)kPending;
 }
 
-// decide(), exact pass (rare): NumPy's float32 exp and add.reduce, float32 divide,
-// float64 cumsum, cdf /= cdf[-1], searchsorted(side="right") on the float64 u53.
+// decide(), exact pass (rare): NumPy's float32 exp and add.reduce, float32 divide, float64
+// cumsum, cdf /= cdf[-1], searchsorted(side="right") on the float64 u53; kNoReq when the sum
+// fails :82 (tested on the cdf total; every such agent arrives here: no_request_sum).
 // Streams over the candidates, re-reading the scores from LDS in each of its passes
 // (max, sum, cdf total, search) with one candidate live at a time: this path sets
 // the kernel's register peak otherwise.  Neumann only (the 8-lane pairwise sum of
@@ -222,7 +223,7 @@ __device__ __forceinline__ uint32_t lane_decide_exact(int pp, int PW, const uint
             }
         }
     }
-    return pick;
+    return no_request_sum(last) ? (uint32_t)kNoReq : pick;               // :82, on the cdf total (no_request_sum)
 }
 
 // The same with every term held (Moore: add.reduce pairs 8 terms).
@@ -253,7 +254,7 @@ __device__ __forceinline__ uint32_t lane_decide_exact_arr(int pp, int PW, const 
             pick = (uint32_t)k;
         }
     }
-    return pick;
+    return no_request_sum(last) ? (uint32_t)kNoReq : pick;               // :82, on the cdf total (no_request_sum)
 }
 
 }  // namespace

@@ -134,6 +134,20 @@ def main():
     m50 = np.load(os.path.join(args.ref, "data/maps/simple_room.npy"))
     s50 = np.load(os.path.join(args.ref, "data/sff/distance_L1.npy"))
     run_case("main_50x50_N100", FloorFieldModel, m50, s50, yaml_params, 100, [42], 100_000, 0)
+    # model/ffm_core.py:82 fails (tests/no_request_util.py): a sealed pocket whose geodesic SFF is inf
+    # (-inf - (-inf); k_S = 0: 0 * inf), the agents in it never request, so the runs are capped at 60
+    # steps; and a cell that only diagonal moves reach, inf in the Neumann field under Moore movement
+    # (a -inf score beside finite ones: probability exactly 0, and :82 passes)
+    import no_request_util as U
+    for nbh, dt, k_S, name in (("neumann", "float32", 3, "pocket_neumann_12x12_N40"),
+                               ("moore", "float32", 3, "pocket_moore_12x12_N40"),
+                               ("neumann", "float64", 3, "pocket_neumann_f64_12x12_N40"),
+                               ("moore", "float32", 0, "pocket_moore_kS0_12x12_N40")):
+        mp, sp = U.pocket_room(nbh, dt)
+        run_case(name, FloorFieldModel, np.array(mp), np.array(sp), U.params(nbh, k_S), 40, list(range(12)), 60, 1)
+    for dt, name in (("float32", "diag_moore_12x12_N60"), ("float64", "diag_moore_f64_12x12_N60")):
+        md, sd = U.diag_room(dt)
+        run_case(name, FloorFieldModel, np.array(md), np.array(sd), U.params("moore"), 60, list(range(4)), 60, 1)
 
 
 if __name__ == "__main__":

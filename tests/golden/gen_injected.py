@@ -7,7 +7,8 @@ Like gen_golden.py it imports ``model.ffm_core.FloorFieldModel`` from the refere
 (SoraKurihara/FFM), but instead of stepping from the model's own placement it overwrites
 ``positions`` and ``dff`` with a state the dynamics do not produce by themselves (the families
 of tests/test_gpu_geometry.py: packed blobs, rings of requesters around one cell, a large
-DFF), seeds both global generators, and records 6 steps.  Only the recorded arrays (inputs and
+DFF; and one DFF cell at 3e38 with k_D = 8, whose product overflows float32, so that the agents
+around it fail model/ffm_core.py:82 and make no request), seeds both global generators, and records 6 steps.  Only the recorded arrays (inputs and
 outputs) are written, as small ``inject_*.npz`` fixtures next to this script.
 
 Fixture layout (one file per case):
@@ -68,7 +69,15 @@ def run_case(name, FloorFieldModel, map_array, sff, params, cells0, dff0, seed):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
+    ap.add_argument("--only", default="", help="a prefix: (re)generate the cases whose names start with it")
     args = ap.parse_args()
+    global run_case
+    _run = run_case
+
+    def run_case(name, *a, **kw):        # noqa: F811 -- filter by --only
+        if name.startswith(args.only):
+            _run(name, *a, **kw)
+
     sys.path.insert(0, args.ref)
     from model.ffm_core import FloorFieldModel  # the reference itself
     sys.path.insert(0, os.path.dirname(TESTS))
@@ -108,6 +117,16 @@ def main():
     cells, dff = injected_state(rng, m, 40, 4, "ring", 200)
     run_case("interior20x24_neumann_ring40_kS10_kD1_s200", FloorFieldModel, m, l1_sff(m),
              {"k_S": 10, "k_D": 1, "diffuse": 0.2, "decay": 0.2, "neighborhood": "neumann"}, cells, dff, 602)
+    # k_D * DFF overflows float32 around one cell: the agents beside it (or on it) make no request
+    import no_request_util as U
+    m = make_named_room("plain")
+    i = 0
+    for nbh in ("neumann", "moore"):
+        for on_cell in (False, True):
+            cells, dff = U.overflow_state(m, 4 if nbh == "neumann" else 8, on_cell, 900 + i)
+            run_case(f"overflow_{nbh}_{'on' if on_cell else 'ring'}60_kS3_kD8", FloorFieldModel, m, l1_sff(m),
+                     {"k_S": 3, "k_D": 8, "diffuse": 0.2, "decay": 0.2, "neighborhood": nbh}, cells, dff, 700 + i)
+            i += 1
 
 
 if __name__ == "__main__":

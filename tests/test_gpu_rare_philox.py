@@ -70,12 +70,36 @@ OTHER_SETS = ({}, {"k_S": 1.5, "k_D": 1, "diffuse": 0.5, "decay": 0.1, "n_agents
               {"k_S": 10, "k_D": 2.5, "diffuse": 0.05, "decay": 0.6, "n_agents": 17})
 
 
+def _layout(form_id, rooms, params, E, N, s, genv, seed, cap=R.A, fix_set=None):
+    """The envs of a case, without an engine: (parameter sets, set of each env, rooms in use, room of
+    each env, oracle mirror).  Envs of one room and one parameter point share an O.Core."""
+    from oracle import oracle as O
+    f = FORMS[form_id]
+    sets_on = f["pep"] is not None or fix_set is not None
+    others = [{**o, "n_agents": min(o["n_agents"], cap)} if "n_agents" in o else o for o in OTHER_SETS]
+    sets = [fix_set or {}] + others if sets_on else [{}]
+    soe = [0 if (e == s or not sets_on) else 1 + e % len(OTHER_SETS) for e in range(E)]
+    rooms = list(rooms) if f["room"] else [rooms[0]]
+    roe = [0 if e == s else e % len(rooms) for e in range(E)]
+    made = {}
+
+    def core(e):
+        p = {**params, **{k: v for k, v in sets[soe[e]].items() if k != "n_agents"}}
+        key = (roe[e], tuple(sorted(p.items())))
+        if key not in made:
+            made[key] = O.Core(np.array(rooms[roe[e]][0]), np.array(rooms[roe[e]][1]), p)
+        return made[key]
+
+    mir = R.Mirror([core(e) for e in range(E)], [sets[soe[e]].get("n_agents", N) for e in range(E)], seed, genv - s,
+                   cap=cap)
+    return sets if sets_on else None, soe, rooms, roe, mir
+
+
 def _case(monkeypatch, form_id, rooms, params, E, N, s, genv, seed, cap=R.A, fix_set=None, setting=None, shards=None):
     """(engine, oracle mirror) of E envs with the env of global id `genv` at local index s.
     rooms: (map, sff) pairs, the first the create-time room and the fixture env's; the others are
     used by the room forms (envs alternate).  fix_set: the fixture env's own parameter set."""
     from ffm_amd.engine import Engine
-    from oracle import oracle as O
     f = FORMS[form_id]
     for k in SWITCHES:
         monkeypatch.delenv(k, raising=False)
@@ -83,16 +107,11 @@ def _case(monkeypatch, form_id, rooms, params, E, N, s, genv, seed, cap=R.A, fix
                  ("FFM_RESET_CANDIDATES", setting), ("FFM_STEP_SHARDS", shards)):
         if v is not None:
             monkeypatch.setenv(k, str(v))
-    sets_on = f["pep"] is not None or fix_set is not None
-    others = [{**o, "n_agents": min(o["n_agents"], cap)} if "n_agents" in o else o for o in OTHER_SETS]
-    sets = [fix_set or {}] + others if sets_on else [{}]
-    soe = [0 if (e == s or not sets_on) else 1 + e % len(OTHER_SETS) for e in range(E)]
-    rooms = list(rooms) if f["room"] else [rooms[0]]
-    roe = [0 if e == s else e % len(rooms) for e in range(E)]
+    sets, soe, rooms, roe, mir = _layout(form_id, rooms, params, E, N, s, genv, seed, cap=cap, fix_set=fix_set)
     env_base = genv - s
     eng = Engine(rooms[0][0], rooms[0][1], n_envs=E, n_agents=N, agent_capacity=cap, params=params, rng="philox",
                  seed=seed, auto_reset=True, env_base=env_base, envs_per_block=f["epb"])
-    if sets_on:
+    if sets is not None:
         eng.set_env_params(sets, np.asarray(soe, np.int32), kernel=f["pep"])
     if f["room"]:
         eng.set_env_rooms(rooms, np.asarray(roe, np.int32), kernel=f["room"])
@@ -105,17 +124,6 @@ def _case(monkeypatch, form_id, rooms, params, E, N, s, genv, seed, cap=R.A, fix
             assert li["group_one"] == (f["one"] is not False), li
             assert f["G"] is None or li["group_g"] == f["G"], li
     assert li["env_rooms"] == (len(rooms) if f["room"] else 0), li
-    made = {}
-
-    def core(e):
-        p = {**params, **{k: v for k, v in sets[soe[e]].items() if k != "n_agents"}}
-        key = (roe[e], tuple(sorted(p.items())))
-        if key not in made:
-            made[key] = O.Core(np.array(rooms[roe[e]][0]), np.array(rooms[roe[e]][1]), p)
-        return made[key]
-
-    mir = R.Mirror([core(e) for e in range(E)], [sets[soe[e]].get("n_agents", N) for e in range(E)], seed, env_base,
-                   cap=cap)
     return eng, mir
 
 

@@ -14,6 +14,10 @@ CASES = case_names()
 def test_cases_present():
     assert {"neumann_12x12_N8", "neumann_12x12_N32", "moore_12x12_N32",
             "main_50x50_N100", "neumann_64x64_N512"} <= set(CASES)
+    # model/ffm_core.py:82 (tests/test_no_request_fixtures.py): the sealed pocket in both neighbourhoods, with a
+    # float64 SFF and with k_S = 0, and the diagonal-only cell in both SFF dtypes
+    assert {"pocket_neumann_12x12_N40", "pocket_moore_12x12_N40", "pocket_neumann_f64_12x12_N40",
+            "pocket_moore_kS0_12x12_N40", "diag_moore_12x12_N60", "diag_moore_f64_12x12_N60"} <= set(CASES)
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -42,6 +46,9 @@ def test_injected_cases_present():
         for nbh in ("neumann", "moore"):
             assert any(n.startswith(f"{room}_{nbh}_") for n in names), (room, nbh)
     assert any(load_inject(n).map.shape == (20, 24) for n in names if "20x24" in n)
+    for nbh in ("neumann", "moore"):      # k_D * DFF overflows float32: beside the hot cell and on it
+        for where in ("ring", "on"):
+            assert f"overflow_{nbh}_{where}60_kS3_kD8" in names
 
 
 @pytest.mark.parametrize("name", inject_names())
