@@ -128,6 +128,16 @@ struct ffm_engine {
     int xf_classes = 0, xf_doors = 0, xf_bins = 0, xf_slots = 0, xf_blocks = 0, xf_rooms = 0;
     bool xf_lds = false;                      // the flow kernel's form
     std::vector<int32_t> xf_door_of_cell;     // [rooms][HW] the labels in effect, -1 off the exits
+    // Motion statistics (ffm_engine_set_motion_stats): null / 0 while off.  They share d_ep_start
+    // with the three features above, and the snapshot d_prev_* with the exit flow: it lives while
+    // either of the two is on.
+    unsigned long long* d_mo_tab = nullptr;   // [mo_slots][mo_classes][core_motion_stride] (kernels.h MotionArgs)
+    int32_t* d_mo_cls = nullptr;              // [n_envs] class of every env, or null (one class)
+    uint8_t* d_mo_dir_from = nullptr;         // [rooms][HW] the direction table
+    uint16_t* d_origin = nullptr;             // sized like d_pos: the cell every agent was placed on
+    uint32_t* d_origin_for = nullptr;         // sized like d_ep_start: the ep_start every origin row belongs to
+    int mo_classes = 0, mo_bins = 0, mo_slots = 0, mo_blocks = 0, mo_rooms = 0;
+    bool mo_lds = false;                      // the motion kernel's form
     std::vector<uint8_t> map0;                // the create-time map, row-major (0 free, 2 blocked, 3 exit)
     // The step plans, one per form (plan() picks), and when each is filled:
     StepPlan create_plan;      // ffm_engine_create: the lane, group, wave or block kernel
@@ -283,10 +293,13 @@ static size_t fs_stride(const ffm_engine* e) { return (size_t)e->HW + 2 * (size_
 // Exit flow on: the flow kernel follows every step launch, and d_ep_start stays.
 static bool exit_flow_on(const ffm_engine* e) { return e->d_xf_tab != nullptr; }
 static size_t xf_words(const ffm_engine* e) { return (size_t)e->xf_classes * e->xf_doors * (1 + (size_t)e->xf_bins); }
-// Either follows every step launch with a kernel of its own, which keeps the engine off the fused path.
-static bool observers_on(const ffm_engine* e) { return field_stats_on(e) || exit_flow_on(e); }
+// Motion statistics on: the motion kernel follows every step launch, and d_ep_start stays.
+static bool motion_stats_on(const ffm_engine* e) { return e->d_mo_tab != nullptr; }
+static size_t mo_stride(const ffm_engine* e) { return ffm::core_motion_stride(e->HW, e->d.neighborhood, e->mo_bins); }
+// Each follows every step launch with a kernel of its own, which keeps the engine off the fused path.
+static bool observers_on(const ffm_engine* e) { return field_stats_on(e) || exit_flow_on(e) || motion_stats_on(e); }
 
-// ep_start_too: unless the field statistics or the exit flow still need it.
+// ep_start_too: unless the field statistics, the exit flow or the motion statistics still need it.
 static void free_episode_log(ffm_engine* e, bool ep_start_too) {
     (void)hipFree(e->d_eplog);
     (void)hipFree(e->d_eplog_n);
@@ -302,18 +315,40 @@ static void free_episode_log(ffm_engine* e, bool ep_start_too) {
     }
 }
 
+// The snapshot of pos, cnt and ep_start: the exit flow's and the motion statistics'.
+static void free_snapshot(ffm_engine* e) {
+    void* bufs[] = {e->d_prev_pos, e->d_prev_cnt, e->d_prev_start};
+    for (void* p : bufs) (void)hipFree(p);
+    e->d_prev_pos = nullptr;
+    e->d_prev_cnt = nullptr;
+    e->d_prev_start = nullptr;
+}
+
+// (the snapshot too, unless the motion statistics still need it)
 static void free_exit_flow(ffm_engine* e) {
-    void* bufs[] = {e->d_xf_tab, e->d_xf_cls, e->d_xf_door_from, e->d_prev_pos, e->d_prev_cnt, e->d_prev_start};
+    void* bufs[] = {e->d_xf_tab, e->d_xf_cls, e->d_xf_door_from};
     for (void* p : bufs) (void)hipFree(p);
     e->d_xf_tab = nullptr;
     e->d_xf_cls = nullptr;
     e->d_xf_door_from = nullptr;
-    e->d_prev_pos = nullptr;
-    e->d_prev_cnt = nullptr;
-    e->d_prev_start = nullptr;
+    if (!motion_stats_on(e)) free_snapshot(e);
     e->xf_classes = e->xf_doors = e->xf_bins = e->xf_slots = e->xf_blocks = e->xf_rooms = 0;
     e->xf_lds = false;
     e->xf_door_of_cell.clear();
+}
+
+// (the snapshot too, unless the exit flow still needs it)
+static void free_motion_stats(ffm_engine* e) {
+    void* bufs[] = {e->d_mo_tab, e->d_mo_cls, e->d_mo_dir_from, e->d_origin, e->d_origin_for};
+    for (void* p : bufs) (void)hipFree(p);
+    e->d_origin_for = nullptr;
+    e->d_mo_tab = nullptr;
+    e->d_mo_cls = nullptr;
+    e->d_mo_dir_from = nullptr;
+    e->d_origin = nullptr;
+    if (!exit_flow_on(e)) free_snapshot(e);
+    e->mo_classes = e->mo_bins = e->mo_slots = e->mo_blocks = e->mo_rooms = 0;
+    e->mo_lds = false;
 }
 
 static void free_field_stats(ffm_engine* e) {
@@ -448,6 +483,7 @@ static void release(ffm_engine* e) {
     free_capture(e);
     free_field_stats(e);
     free_exit_flow(e);
+    free_motion_stats(e);
     free_episode_log(e, true);
     delete e;
 }
@@ -760,11 +796,42 @@ static hipError_t launch_flow(const ffm_engine* e, const ffm::CoreStepArgs& a, l
     return ffm::launch_core_flow(f, e->xf_lds, e->xf_blocks, s);
 }
 
-// The exit flow's snapshot invariant: whoever writes pos, cnt or ep_start ends with this, on the
-// same stream (the flow kernel carries the snapshot forward itself).  Whole arrays: the envs a
-// call left alone hold equal data already.  Nothing while the feature is off.
+// The motion statistics' kernel (core_motion.hip) after the step launch `a` describes, as
+// launch_flow; before the flow's, and carrying the snapshot forward only where the flow is off.
+static hipError_t launch_motion(const ffm_engine* e, const ffm::CoreStepArgs& a, long long e0, hipStream_t s) {
+    ffm::MotionArgs m{};
+    m.pos = a.pos;
+    m.cnt = a.cnt;
+    m.ep_start = a.ep_start;
+    m.prev_pos = e->d_prev_pos + e0 * a.A;
+    m.prev_cnt = e->d_prev_cnt + e0;
+    m.prev_start = e->d_prev_start + e0;
+    m.origin = e->d_origin + e0 * a.A;
+    m.origin_for = e->d_origin_for + e0;
+    m.cls = e->d_mo_cls ? e->d_mo_cls + e0 : nullptr;
+    m.room_of_env = a.room_of_env;
+    m.dir_from = e->d_mo_dir_from;
+    m.tab = e->d_mo_tab;
+    m.E = a.E;
+    m.A = a.A;
+    m.HW = a.HW;
+    m.W = e->d.W;
+    m.R = e->mo_rooms;
+    m.bins = e->mo_bins;
+    m.C = e->mo_classes;
+    m.NB = e->d.neighborhood;
+    m.slots = e->mo_slots;
+    m.carry = exit_flow_on(e) ? 0 : 1;
+    m.t = a.t;
+    return ffm::launch_core_motion(m, e->mo_lds, e->mo_blocks, s);
+}
+
+// The snapshot invariant of the exit flow and the motion statistics: whoever writes pos, cnt or
+// ep_start ends with this, on the same stream (the flow kernel, or without it the motion kernel,
+// carries the snapshot forward itself).  Whole arrays: the envs a call left alone hold equal data
+// already.  Nothing while both features are off.
 static hipError_t refresh_flow_snapshot(ffm_engine* e, hipStream_t s) {
-    if (!exit_flow_on(e)) return hipSuccess;
+    if (!exit_flow_on(e) && !motion_stats_on(e)) return hipSuccess;
     const size_t Ep = ((size_t)e->d.n_envs + 7) & ~(size_t)7;
     hipError_t he = hipMemcpyAsync(e->d_prev_pos, e->d_pos, Ep * e->d.agent_capacity * 2, hipMemcpyDeviceToDevice, s);
     if (he == hipSuccess) he = hipMemcpyAsync(e->d_prev_cnt, e->d_cnt, Ep * 4, hipMemcpyDeviceToDevice, s);
@@ -776,8 +843,8 @@ static hipError_t refresh_flow_snapshot(ffm_engine* e, hipStream_t s) {
 // step over all envs) with trajectory capture on (its kernel follows every step launch on the
 // caller's stream), on the fused multi-step path and with per-env parameters on the lane kernel
 // (only plans of the group kernel hold shards; its per-env and room forms hold their own).
-// Field statistics and the exit flow keep the shards (their kernels follow each shard's launch on
-// that shard's stream) and keep the engine off the fused path.
+// Field statistics, the exit flow and the motion statistics keep the shards (their kernels follow
+// each shard's launch on that shard's stream) and keep the engine off the fused path.
 static int shards_in_effect(const ffm_engine* e) {
     const size_t S = plan(e).shards.size();
     if (S <= 1 || e->cap.n_sel != 0 || (e->fused > 1 && e->multi && !rooms_on(e) && !observers_on(e))) return 1;
@@ -818,6 +885,7 @@ static int step_sharded(ffm_engine* e, int32_t n_steps, hipStream_t s) {
             he = ffm::launch_core_group(a, e->d.neighborhood, sh.blocks, k ? e->sh_stream[k - 1] : s, sh.g, p.one);
             // the shards add to the same slot copies: every add to them is an atomic
             if (he == hipSuccess && field_stats_on(e)) he = launch_observer(e, a, sh.e0, k ? e->sh_stream[k - 1] : s);
+            if (he == hipSuccess && motion_stats_on(e)) he = launch_motion(e, a, sh.e0, k ? e->sh_stream[k - 1] : s);
             if (he == hipSuccess && exit_flow_on(e)) he = launch_flow(e, a, sh.e0, k ? e->sh_stream[k - 1] : s);
         }
     }
@@ -869,6 +937,7 @@ int ffm_engine_step(ffm_engine* e, int32_t n_steps, void* stream) {
         }
         if (e->cap.n_sel) HIP_TRY(ffm::launch_core_capture(a, e->cap, s));
         if (field_stats_on(e)) HIP_TRY(launch_observer(e, a, 0, s));
+        if (motion_stats_on(e)) HIP_TRY(launch_motion(e, a, 0, s));
         if (exit_flow_on(e)) HIP_TRY(launch_flow(e, a, 0, s));
         e->t++;
     }
@@ -904,6 +973,10 @@ int ffm_engine_reset(ffm_engine* e, void* stream) {
     e->t++;
     if (e->cap.n_sel) HIP_TRY(ffm::launch_core_capture_init(make_args(e), e->cap, s));
     HIP_TRY(refresh_flow_snapshot(e, s));
+    // motion statistics: no origin row is of the episodes just placed (ep_start is the index consumed
+    // above), whatever the step index was set to before the call
+    if (motion_stats_on(e))
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)e->d_origin_for, (int)(e->t - 2u), ((size_t)E + 7) & ~(size_t)7, s));
     return FFM_OK;
 }
 
@@ -1444,6 +1517,7 @@ int ffm_engine_set_exit_flow(ffm_engine* e, const int32_t* door_of_cell, int32_t
         return fail(nomem ? FFM_E_NOMEM : FFM_E_HIP, std::string("exit flow: ") + hipGetErrorString(he));
     }
     free_exit_flow(e);
+    free_snapshot(e);                        // (shared with the motion statistics: the new one holds the same state)
     e->d_xf_tab = tab;
     e->d_xf_cls = cls;
     e->d_xf_door_from = d_dfrom;
@@ -1504,6 +1578,176 @@ int ffm_debug_exit_flow_info(ffm_engine* e, int32_t* out, int n) {
         e->xf_doors,
         e->xf_bins,
         e->xf_rooms,
+    };
+    for (int i = 0; i < n; i++) out[i] = v[i];
+    return FFM_OK;
+}
+
+// dir_from of one room (kernels.h MotionArgs): build_door_from's rule, but the neighbour index of
+// the first exit cell instead of its door.
+static void build_dir_from(const uint8_t* map, int H, int W, int nb, uint8_t* out) {
+    static const int dx4[4] = {-1, 1, 0, 0}, dy4[4] = {0, 0, -1, 1};
+    static const int dx8[8] = {-1, -1, -1, 0, 0, 1, 1, 1}, dy8[8] = {-1, 0, 1, -1, 1, -1, 0, 1};
+    const int* dx = nb == 4 ? dx4 : dx8;
+    const int* dy = nb == 4 ? dy4 : dy8;
+    for (int x = 0; x < H; x++)
+        for (int y = 0; y < W; y++) {
+            uint8_t d = 0xFF;
+            if (map[x * W + y] == 0)
+                for (int k = 0; k < nb && d == 0xFF; k++) {
+                    const int u = x + dx[k], v = y + dy[k];
+                    if (u >= 0 && u < H && v >= 0 && v < W && map[u * W + v] == 3) d = (uint8_t)k;
+                }
+            out[x * W + y] = d;
+        }
+}
+
+int ffm_engine_set_motion_stats(ffm_engine* e, const int32_t* class_of_env, int32_t n_classes, int32_t curve_bins,
+                                void* stream) {
+    if (!e) return fail(FFM_E_INVALID, "null engine");
+    if (e->mt) return fail(FFM_E_UNSUPPORTED, "motion statistics: Philox engines only");
+    if (n_classes < 0 || curve_bins < 0) return fail(FFM_E_INVALID, "motion statistics: negative class or bin count");
+    hipStream_t s = (hipStream_t)stream;
+    if (n_classes == 0) {
+        HIP_TRY(hipStreamSynchronize(s));    // queued motion kernels may still write the tables
+        free_motion_stats(e);
+        if (!e->d_eplog && !e->d_ephist) free_episode_log(e, true);   // ep_start, unless another observer needs it
+        return FFM_OK;
+    }
+    const size_t E = (size_t)e->d.n_envs;
+    const int HW = e->HW, A = e->d.agent_capacity, NB = e->d.neighborhood;
+    if (class_of_env)
+        for (size_t i = 0; i < E; i++)
+            if (class_of_env[i] < 0 || class_of_env[i] >= n_classes)
+                return fail(FFM_E_INVALID, "motion statistics: class_of_env entry outside [0, n_classes)");
+    // one copy of the tables as u64, against FFM_MOTION_STATS_MAX_BYTES
+    const size_t words = (size_t)n_classes * ffm::core_motion_stride(HW, NB, curve_bins);
+    if (words * 8 > (size_t)FFM_MOTION_STATS_MAX_BYTES)
+        return fail(FFM_E_INVALID, "motion statistics: n_classes * (H * W * (neighbours + 3) + 2 * curve_bins) * 8 exceeds "
+                                   "FFM_MOTION_STATS_MAX_BYTES");
+    // The form.  FFM_MOTION_STATS_FORM=lds|global forces one, FFM_MOTION_STATS_BLOCKS caps the grid
+    // (A/B and test switches, read here).
+    const int blocks = fs_env_int("FFM_MOTION_STATS_BLOCKS", ffm::kMotionMaxBlocks, 1, 65535);
+    const bool fits = (size_t)n_classes * ffm::core_motion_lds_stride(HW, NB, curve_bins) * 4 <= ffm::kObserveLdsBudget &&
+                      ffm::core_motion_lds_safe(e->d.n_envs, A);
+    bool lds = fits;
+    if (const char* ov = std::getenv("FFM_MOTION_STATS_FORM")) {
+        if (!std::strcmp(ov, "lds")) {
+            if (!fits) return fail(FFM_E_INVALID, "motion statistics: FFM_MOTION_STATS_FORM=lds, but the tables exceed the LDS budget");
+            lds = true;
+        } else if (!std::strcmp(ov, "global")) {
+            lds = false;
+        }
+    }
+    int slots = ffm::kMotionSlots;   // a power of two, fewer where the copies together would pass the limit
+    while (slots > 1 && words * 8 * (size_t)slots > (size_t)FFM_MOTION_STATS_MAX_BYTES) slots /= 2;
+    // the direction table of every room in effect
+    const int R = rooms_on(e) ? (int)e->room_f.size() : 1;
+    const uint8_t* maps = rooms_on(e) ? e->room_maps.data() : e->map0.data();
+    std::vector<uint8_t> dfrom((size_t)R * HW);
+    for (int r = 0; r < R; r++) build_dir_from(maps + (size_t)r * HW, e->d.H, e->d.W, NB, dfrom.data() + (size_t)r * HW);
+
+    HIP_TRY(hipStreamSynchronize(s));        // queued motion kernels may still write the old tables
+    // Build into locals; the engine changes after the last call that can fail.
+    unsigned long long* tab = nullptr;
+    int32_t* cls = nullptr;
+    uint8_t* d_dfrom = nullptr;
+    uint16_t* origin = nullptr;
+    uint32_t* origin_for = nullptr;
+    uint16_t* ppos = nullptr;
+    int32_t* pcnt = nullptr;
+    uint32_t* pstart = nullptr;
+    uint32_t* ep_start = nullptr;
+    const bool fresh = e->d_ep_start == nullptr;
+    const size_t Ep = (E + 7) & ~(size_t)7;   // padded like d_cnt
+    hipError_t he = hipMalloc((void**)&tab, words * 8 * (size_t)slots);
+    if (he == hipSuccess && class_of_env) he = hipMalloc((void**)&cls, E * 4);
+    if (he == hipSuccess) he = hipMalloc((void**)&d_dfrom, dfrom.size());
+    if (he == hipSuccess) he = hipMalloc((void**)&origin, Ep * A * 2 + 512);   // sized like d_pos
+    if (he == hipSuccess) he = hipMalloc((void**)&origin_for, Ep * 4);
+    if (he == hipSuccess) he = hipMalloc((void**)&ppos, Ep * A * 2 + 512);
+    if (he == hipSuccess) he = hipMalloc((void**)&pcnt, Ep * 4);
+    if (he == hipSuccess) he = hipMalloc((void**)&pstart, Ep * 4);
+    if (he == hipSuccess && fresh) he = hipMalloc((void**)&ep_start, Ep * 4);
+    const bool nomem = he != hipSuccess;
+    if (he == hipSuccess) he = hipMemsetAsync(tab, 0, words * 8 * (size_t)slots, s);
+    if (he == hipSuccess && cls) he = hipMemcpyAsync(cls, class_of_env, E * 4, hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(d_dfrom, dfrom.data(), dfrom.size(), hipMemcpyHostToDevice, s);
+    // Turned on mid-run: episodes in flight count from here, as the episode log's do (the next
+    // step is keyed e->t, so the index that "placed" every env is the one before it) ...
+    if (he == hipSuccess && fresh) he = hipMemsetD32Async((hipDeviceptr_t)ep_start, (int)(e->t - 1u), Ep, s);
+    // ... and agents in flight originate where they stand now: rows of the episodes in flight
+    if (he == hipSuccess) he = hipMemcpyAsync(origin, e->d_pos, Ep * A * 2, hipMemcpyDeviceToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(origin_for, fresh ? ep_start : e->d_ep_start, Ep * 4, hipMemcpyDeviceToDevice, s);
+    // the snapshot: the state as it stands (with the exit flow on, what its snapshot holds already)
+    if (he == hipSuccess) he = hipMemcpyAsync(ppos, e->d_pos, Ep * A * 2, hipMemcpyDeviceToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(pcnt, e->d_cnt, Ep * 4, hipMemcpyDeviceToDevice, s);
+    if (he == hipSuccess) he = hipMemcpyAsync(pstart, fresh ? ep_start : e->d_ep_start, Ep * 4, hipMemcpyDeviceToDevice, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    if (he != hipSuccess) {
+        void* bufs[] = {tab, cls, d_dfrom, origin, origin_for, ppos, pcnt, pstart, ep_start};
+        for (void* p : bufs) (void)hipFree(p);
+        return fail(nomem ? FFM_E_NOMEM : FFM_E_HIP, std::string("motion statistics: ") + hipGetErrorString(he));
+    }
+    free_motion_stats(e);
+    free_snapshot(e);                        // (shared with the exit flow: the new one holds the same state)
+    e->d_mo_tab = tab;
+    e->d_mo_cls = cls;
+    e->d_mo_dir_from = d_dfrom;
+    e->d_origin = origin;
+    e->d_origin_for = origin_for;
+    e->d_prev_pos = ppos;
+    e->d_prev_cnt = pcnt;
+    e->d_prev_start = pstart;
+    if (fresh) e->d_ep_start = ep_start;
+    e->mo_classes = n_classes;
+    e->mo_bins = curve_bins;
+    e->mo_slots = slots;
+    e->mo_blocks = blocks;
+    e->mo_rooms = R;
+    e->mo_lds = lds;
+    return FFM_OK;
+}
+
+int ffm_engine_get_motion_stats(ffm_engine* e, uint64_t* flux, uint64_t* present, uint64_t* moved, uint64_t* egress_count,
+                                uint64_t* egress_steps, int32_t clear, void* stream) {
+    if (!e) return fail(FFM_E_INVALID, "null engine");
+    if (!motion_stats_on(e)) return fail(FFM_E_INVALID, "the motion statistics are off");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t S = mo_stride(e), C = (size_t)e->mo_classes, HW = (size_t)e->HW, bins = (size_t)e->mo_bins;
+    const size_t F = HW * ((size_t)e->d.neighborhood + 1), words = C * S;
+    std::vector<unsigned long long> h(words * (size_t)e->mo_slots);
+    HIP_TRY(hipMemcpyAsync(h.data(), e->d_mo_tab, h.size() * 8, hipMemcpyDeviceToHost, s));
+    if (clear) HIP_TRY(hipMemsetAsync(e->d_mo_tab, 0, h.size() * 8, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int k = 1; k < e->mo_slots; k++)
+        for (size_t i = 0; i < words; i++) h[i] += h[(size_t)k * words + i];
+    for (size_t c = 0; c < C; c++) {
+        const unsigned long long* T = h.data() + c * S;
+        if (flux) std::copy(T, T + F, flux + c * F);
+        if (present) std::copy(T + F, T + F + bins, present + c * bins);
+        if (moved) std::copy(T + F + bins, T + F + 2 * bins, moved + c * bins);
+        if (egress_count) std::copy(T + F + 2 * bins, T + F + 2 * bins + HW, egress_count + c * HW);
+        if (egress_steps) std::copy(T + F + 2 * bins + HW, T + S, egress_steps + c * HW);
+    }
+    return FFM_OK;
+}
+
+// Diagnostic (not part of the ABI header): the motion statistics in effect.
+//   out[0] 0 off, 1 the LDS form, 2 the global form;  out[1] blocks of the motion kernel's grid over
+//   all envs;  out[2] slot copies of the tables;  out[3] classes;  out[4] curve bins;  out[5] rooms
+//   of the direction table;  out[6] directions per cell (neighbours + 1)
+int ffm_debug_motion_stats_info(ffm_engine* e, int32_t* out, int n) {
+    if (!e || !out || n < 0 || n > 7) return fail(FFM_E_INVALID, "bad args");
+    const bool on = motion_stats_on(e);
+    const int32_t v[7] = {
+        !on ? 0 : e->mo_lds ? 1 : 2,
+        on ? ffm::core_motion_grid(e->d.n_envs, e->d.agent_capacity, e->mo_blocks) : 0,
+        e->mo_slots,
+        e->mo_classes,
+        e->mo_bins,
+        e->mo_rooms,
+        e->d.neighborhood + 1,
     };
     for (int i = 0; i < n; i++) out[i] = v[i];
     return FFM_OK;
@@ -1715,6 +1959,7 @@ int ffm_engine_set_env_rooms(ffm_engine* e, const uint8_t* maps, const float* sf
     if (!e) return fail(FFM_E_INVALID, "null engine");
     // the door table is built from the rooms in effect when the flow is set: rooms first, the flow after
     if (exit_flow_on(e)) return fail(FFM_E_INVALID, "env rooms: the exit flow is on (turn it off, set the rooms, set it again)");
+    if (motion_stats_on(e)) return fail(FFM_E_INVALID, "env rooms: the motion statistics are on (turn them off, set the rooms, set them again)");
     hipStream_t s = (hipStream_t)stream;
     const size_t E = (size_t)e->d.n_envs;
     const bool pep = pep_on(e);

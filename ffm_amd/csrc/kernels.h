@@ -187,6 +187,39 @@ int core_flow_grid(long long E, int A, int max_blocks);
 bool core_flow_lds_safe(long long E, int A);
 hipError_t launch_core_flow(const FlowArgs& f, bool lds, int max_blocks, hipStream_t s);
 
+// Motion statistics (ffm_engine_set_motion_stats; core_motion.hip): what the motion kernel launched
+// after a step launch reads -- the flow kernel's inputs, with the direction table in the place of
+// the door table -- the origin row it compacts in place and the tables it adds to.  One class is
+//   flux[HW][NB + 1], present[bins], moved[bins], egress_count[HW], egress_steps[HW]
+// (core_motion_stride words); `tab` holds `slots` (a power of two) copies of the C classes, summed
+// by the host when it reads.  The kernel runs before the flow kernel and carries the snapshot
+// forward (as the flow kernel does) only where `carry` says the flow is off.
+struct MotionArgs {
+    const uint16_t* pos;           // [E][A] after the step
+    const int* cnt;                // [E]
+    const uint32_t* ep_start;      // [E]
+    uint16_t* prev_pos;            // [E][A] before the step; with carry, after the kernel: pos
+    int* prev_cnt;                 // [E]
+    uint32_t* prev_start;          // [E]
+    uint16_t* origin;              // [E][A] the cell the agent now at an index was placed on
+    uint32_t* origin_for;          // [E] the ep_start of the episode the origin row belongs to
+    const int* cls;                // [E] class of every env, or nullptr (class 0)
+    const int* room_of_env;        // [E] or nullptr (room 0)
+    const uint8_t* dir_from;       // [R][HW] neighbour index of the first exit among a cell's neighbours, 0xFF: none
+    unsigned long long* tab;       // [slots][C][core_motion_stride]
+    long long E;
+    int A, HW, W, R, bins, C, NB, slots, carry;
+    uint32_t t;                    // the step index that keyed the step launch
+};
+constexpr int kMotionSlots = 16, kMotionMaxBlocks = 1024;
+// Words of one class: in the tables, and in the LDS form's block copy (egress_steps, the last
+// part, is not kept there: its adds go straight to the u64 tables).
+inline size_t core_motion_stride(int HW, int NB, int bins) { return (size_t)HW * (NB + 1) + 2 * (size_t)bins + 2 * (size_t)HW; }
+inline size_t core_motion_lds_stride(int HW, int NB, int bins) { return core_motion_stride(HW, NB, bins) - (size_t)HW; }
+int core_motion_grid(long long E, int A, int max_blocks);
+bool core_motion_lds_safe(long long E, int A);
+hipError_t launch_core_motion(const MotionArgs& m, bool lds, int max_blocks, hipStream_t s);
+
 size_t core_wave_smem_bytes(int H, int W, int A, int F, bool mt, bool reset, int waves);
 size_t core_block_smem_bytes(int H, int W, int A, int K, int F, bool f64, bool mt, bool reset);
 hipError_t launch_core_wave(const CoreStepArgs& a, int nb, bool mt, int blocks, hipStream_t s);

@@ -32,6 +32,7 @@ EXPORTED = [
     "ffm_engine_set_episode_log", "ffm_engine_drain_episodes", "ffm_engine_get_episode_stats",
     "ffm_engine_set_field_stats", "ffm_engine_get_field_stats",
     "ffm_engine_set_exit_flow", "ffm_engine_get_exit_flow", "ffm_engine_get_exit_doors",
+    "ffm_engine_set_motion_stats", "ffm_engine_get_motion_stats",
     "ffm_debug_stage_image", "ffm_debug_reset_candidates",
     "ffm_engine_set_env_params", "ffm_engine_get_env_params", "ffm_engine_set_env_params_kernel",
     "ffm_engine_set_env_rooms", "ffm_engine_get_env_rooms", "ffm_engine_set_env_rooms_kernel",
@@ -157,6 +158,8 @@ def load_library():
     L.ffm_engine_set_exit_flow.argtypes = [P, P, i32, P, i32, i32, P]
     L.ffm_engine_get_exit_flow.argtypes = [P, P, P, i32, P]
     L.ffm_engine_get_exit_doors.argtypes = [P, P, C.POINTER(i32)]
+    L.ffm_engine_set_motion_stats.argtypes = [P, P, i32, i32, P]
+    L.ffm_engine_get_motion_stats.argtypes = [P, P, P, P, P, P, i32, P]
     L.ffm_engine_set_env_params.argtypes = [P, C.POINTER(EnvParams), i32, P, P]
     L.ffm_engine_get_env_params.argtypes = [P, C.POINTER(EnvParams), i32, C.POINTER(i32), P]
     L.ffm_engine_set_env_params_kernel.argtypes = [P, i32]
@@ -286,6 +289,15 @@ class _DevArray:
 
 
 DEFAULT_PARAMS = {"k_S": 3, "k_D": 1, "diffuse": 0.2, "decay": 0.2, "neighborhood": "moore"}
+
+
+def motion_directions(neighbours: int) -> list:
+    """The (d row, d col) of the motion statistics' direction codes 0 .. neighbours: the reference's
+    neighbour order (model/ffm_core.py:28-34: Neumann up, down, left, right; Moore row-major), then
+    (0, 0), the stay."""
+    if neighbours == 4:
+        return [(-1, 0), (1, 0), (0, -1), (0, 1), (0, 0)]
+    return [(dx, dy) for dx in (-1, 0, 1) for dy in (-1, 0, 1) if (dx, dy) != (0, 0)] + [(0, 0)]
 
 
 class Engine:
@@ -707,6 +719,63 @@ class Engine:
                                                 _stream_handle(stream)))
         _check(self._L.ffm_engine_get_exit_doors(self._h, _ptr(doc), None))
         return {"exited": exited, "outflow": outflow, "door_of_cell": doc}
+
+    # -- motion statistics -------------------------------------------------------
+    def _motion_stats_info(self) -> np.ndarray:
+        # bound here, as group_occupancy()'s: a diagnostic outside the ABI header
+        v = np.zeros(7, np.int32)
+        fn = self._L.ffm_debug_motion_stats_info
+        fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_int], C.c_int
+        _check(fn(self._h, _ptr(v), len(v)))
+        return v
+
+    def motion_stats_info(self):
+        """"off", or with set_motion_stats() on a dict of the motion kernel's form ("lds" or
+        "global"), its grid's blocks over all envs, the tables' slot copies, the classes and the
+        curve bins (diagnostic, ffm_debug_motion_stats_info; kept out of launch_info(), whose dict
+        is compared with recorded ones)."""
+        v = self._motion_stats_info()
+        return "off" if v[0] == 0 else {"form": ("lds", "global")[int(v[0]) - 1], "blocks": int(v[1]),
+                                        "slots": int(v[2]), "classes": int(v[3]), "curve_bins": int(v[4])}
+
+    def set_motion_stats(self, classes=None, n_classes: int | None = None, curve_bins: int = 0, stream=None):
+        """Sum, on the device and per class of envs, how the crowd moves: the flow field, mean
+        speed against the time since placement and the egress time by starting cell (what the
+        reference's users read off the per-step position log); see ffm_engine_set_motion_stats.
+        `classes` / `n_classes` as set_field_stats (0 = off); `curve_bins` > 0 adds `present` and
+        `moved` over the steps since placement (the last bin holds every later step).  Set the
+        rooms first (set_env_rooms raises ValueError while this is on).  While on, step(n) takes one
+        launch per step (no fused steps) and a motion launch follows each; read with
+        motion_stats()."""
+        cls = None
+        if classes is not None:
+            cls = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1)
+            if cls.size != self.n_envs:
+                raise ValueError(f"classes must have n_envs = {self.n_envs} entries, got {cls.size}")
+        if n_classes is None:
+            n_classes = 1 if cls is None else int(cls.max()) + 1
+        _check(self._L.ffm_engine_set_motion_stats(self._h, _ptr(cls), int(n_classes), int(curve_bins),
+                                                   _stream_handle(stream)))
+
+    def motion_stats(self, clear: bool = False, stream=None) -> dict:
+        """The motion statistics as uint64 arrays: flux [C, H, W, NB + 1] (agents that stepped out
+        of a cell in each direction; the last entry: stood still), present and moved [C, bins]
+        (agents inside before a step and those of them that moved, by steps since placement: moved /
+        present is the mean speed; empty without curve_bins), egress_count and egress_steps
+        [C, H, W] (agents placed on a cell that have left, and the sum of their egress times), and
+        `directions`, the (d row, d col) of every flux entry in the reference's neighbour order with
+        (0, 0) last.  clear=True zeroes the counts after the read."""
+        v = self._motion_stats_info()
+        c, bins, nd = (int(v[3]), int(v[4]), int(v[6])) if v[0] else (0, 0, 1)
+        flux = np.zeros((c, self.H, self.W, nd), np.uint64)
+        present = np.zeros((c, bins), np.uint64)
+        moved = np.zeros((c, bins), np.uint64)
+        count = np.zeros((c, self.H, self.W), np.uint64)
+        steps = np.zeros((c, self.H, self.W), np.uint64)
+        _check(self._L.ffm_engine_get_motion_stats(self._h, _ptr(flux), _ptr(present), _ptr(moved), _ptr(count),
+                                                   _ptr(steps), int(bool(clear)), _stream_handle(stream)))
+        return {"flux": flux, "present": present, "moved": moved, "egress_count": count, "egress_steps": steps,
+                "directions": motion_directions(nd - 1)}
 
     def run_episodes(self, per_env: int = 1, max_steps: int | None = None, chunk: int = 16, stream=None) -> np.ndarray:
         """Step until every env has logged `per_env` episodes and return their lengths, int32

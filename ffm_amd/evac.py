@@ -64,6 +64,17 @@ door is) and, with ``--curve-bins B``, ``outflow.csv`` (``set,door,tau,exited``:
 through the door tau steps after placement; the last tau holds every later step too).
 
     python -m ffm_amd.evac --room 12 12 --sweep exit_width=1,2,4 --flow --curve-bins 128 --envs 4096 --out runs/flow
+
+``--motion`` adds how the crowd moves (what ``visualize_trajectory.py`` and ``inspect_trajectory.py``
+show from the position log), summed on the device (``Engine.set_motion_stats``) with one class per
+sweep combination.  It writes ``flux.npy`` ([P, H, W, NB + 1] uint64: agents that stepped out of a
+cell in each direction of the reference's neighbour order, the last entry those that stood still),
+``flux.csv`` (``set,row,col,direction,count``, the non-zero entries), ``egress_by_origin.csv``
+(``set,row,col,count,steps_sum``: the agents placed on a cell that have left and the sum of their
+egress times, for the cells with any) and, with ``--curve-bins B``, ``speed.csv``
+(``set,tau,present,moved``: moved / present is the mean speed tau steps after placement).
+
+    python -m ffm_amd.evac --room 12 12 --sweep exit_width=1,2,4 --motion --curve-bins 128 --envs 4096 --out runs/motion
 """
 from __future__ import annotations
 
@@ -297,6 +308,47 @@ def outflow_csv(outflow) -> str:
     return "\n".join(lines) + "\n"
 
 
+def flux_csv(flux) -> str:
+    """The text of flux.csv from Engine.motion_stats()["flux"] [P, H, W, NB + 1]:
+    ``set,row,col,direction,count``, one row per non-zero entry in (set, row, col, direction) order
+    (direction: the index into motion_stats()["directions"], the last one a stay; flux.npy holds
+    the whole array)."""
+    fx = np.asarray(flux)
+    if fx.ndim != 4:
+        raise ValueError("flux is a [sets, H, W, directions] array")
+    lines = ["set,row,col,direction,count"]
+    for p, x, y, d in np.argwhere(fx != 0).tolist():
+        lines.append(f"{p},{x},{y},{d},{int(fx[p, x, y, d])}")
+    return "\n".join(lines) + "\n"
+
+
+def speed_csv(present, moved) -> str:
+    """The text of speed.csv from Engine.motion_stats()' curves [P, bins]: ``set,tau,present,moved``
+    for every set and every tau = 0 .. bins - 1 (tau: steps since the placement; the last holds
+    every later step too; nothing is counted at tau = 0).  moved / present is the mean speed."""
+    pr, mv = np.asarray(present), np.asarray(moved)
+    if pr.shape != mv.shape or pr.ndim != 2:
+        raise ValueError("present and moved are [sets, bins] arrays of one shape")
+    lines = ["set,tau,present,moved"]
+    for p in range(pr.shape[0]):
+        for tau in range(pr.shape[1]):
+            lines.append(f"{p},{tau},{int(pr[p, tau])},{int(mv[p, tau])}")
+    return "\n".join(lines) + "\n"
+
+
+def egress_by_origin_csv(egress_count, egress_steps) -> str:
+    """The text of egress_by_origin.csv from Engine.motion_stats()' egress tables [P, H, W]:
+    ``set,row,col,count,steps_sum``, one row per cell that agents who left were placed on, in (set,
+    row, col) order.  steps_sum / count is the mean egress time from the cell."""
+    ct, st = np.asarray(egress_count), np.asarray(egress_steps)
+    if ct.shape != st.shape or ct.ndim != 3:
+        raise ValueError("egress_count and egress_steps are [sets, H, W] arrays of one shape")
+    lines = ["set,row,col,count,steps_sum"]
+    for p, x, y in np.argwhere(ct != 0).tolist():
+        lines.append(f"{p},{x},{y},{int(ct[p, x, y])},{int(st[p, x, y])}")
+    return "\n".join(lines) + "\n"
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--map", help=".npy map (0 free, 2 wall, 3 exit)")
@@ -332,9 +384,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--flow", action="store_true",
                     help="also write the on-device exit flow (Engine.set_exit_flow), one class per sweep "
                          "combination: exit_usage.csv, doors.csv")
+    ap.add_argument("--motion", action="store_true",
+                    help="also write the on-device motion statistics (Engine.set_motion_stats), one class per sweep "
+                         "combination: flux.npy, flux.csv, egress_by_origin.csv")
     ap.add_argument("--curve-bins", type=int, default=0, metavar="B",
-                    help="with --fields or --flow: the curves over tau = 0 .. B - 1 steps since placement "
-                         "(remaining.csv, outflow.csv)")
+                    help="with --fields, --flow or --motion: the curves over tau = 0 .. B - 1 steps since placement "
+                         "(remaining.csv, outflow.csv, speed.csv)")
     ap.add_argument("--out", required=True, metavar="DIR")
     return ap
 
@@ -342,8 +397,8 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
-    if a.curve_bins < 0 or (a.curve_bins and not (a.fields or a.flow)):
-        ap.error("--curve-bins B wants B >= 0 and --fields or --flow")
+    if a.curve_bins < 0 or (a.curve_bins and not (a.fields or a.flow or a.motion)):
+        ap.error("--curve-bins B wants B >= 0 and --fields, --flow or --motion")
     if sum(map(bool, (a.map, a.room, a.rooms))) != 1 or (a.rooms and a.sff):
         ap.error("give either --map and --sff, or --room H W, or --rooms MAP.npy:SFF.npy ...")
     try:
@@ -415,6 +470,8 @@ def main(argv=None):
                             curve_bins=a.curve_bins)
     if a.flow:     # after the rooms: the doors are those of the rooms in effect
         eng.set_exit_flow(classes=soe if sets else None, n_classes=len(sets) if sets else 1, curve_bins=a.curve_bins)
+    if a.motion:   # after the rooms too: the direction table is that of the rooms in effect
+        eng.set_motion_stats(classes=soe if sets else None, n_classes=len(sets) if sets else 1, curve_bins=a.curve_bins)
     eng.reset()
     t0 = time.perf_counter()
     steps = eng.run_episodes(per_env=a.episodes, max_steps=a.max_steps)
@@ -422,6 +479,7 @@ def main(argv=None):
     taken = eng.counters()["steps"]
     fields = eng.field_stats() if a.fields else None
     flow = eng.exit_flow() if a.flow else None
+    motion = eng.motion_stats() if a.motion else None
     eng.close()
 
     os.makedirs(a.out, exist_ok=True)
@@ -437,6 +495,15 @@ def main(argv=None):
         texts = {"exit_usage.csv": exit_usage_csv(flow["exited"]), "doors.csv": doors_csv(flow["door_of_cell"])}
         if a.curve_bins > 0:
             texts["outflow.csv"] = outflow_csv(flow["outflow"])
+        for name, body in texts.items():
+            with open(os.path.join(a.out, name), "w") as f:
+                f.write(body)
+    if motion is not None:
+        np.save(os.path.join(a.out, "flux.npy"), motion["flux"])
+        texts = {"flux.csv": flux_csv(motion["flux"]),
+                 "egress_by_origin.csv": egress_by_origin_csv(motion["egress_count"], motion["egress_steps"])}
+        if a.curve_bins > 0:
+            texts["speed.csv"] = speed_csv(motion["present"], motion["moved"])
         for name, body in texts.items():
             with open(os.path.join(a.out, name), "w") as f:
                 f.write(body)

@@ -332,6 +332,62 @@ int ffm_engine_get_exit_flow(ffm_engine* eng, uint64_t* exited, uint64_t* outflo
  * rooms) and *n_doors = D (either may be NULL).  Feature off: FFM_E_INVALID. */
 int ffm_engine_get_exit_doors(ffm_engine* eng, int32_t* door_of_cell, int32_t* n_doors);
 
+/* Motion statistics: how the crowd moves, summed on the device -- the flow field, mean speed
+ * against the time since placement, and the egress time by starting cell (what the reference's
+ * users read off the per-step position log with visualize_trajectory.py and
+ * inspect_trajectory.py).  A kernel follows every step launch and compares the positions before
+ * (P, n0 agents) and after it (P', n agents); nothing leaves the device and no step kernel changes.
+ *
+ * Identity.  The reference removes the agents that reached an exit order-preservingly
+ * (model/ffm_core.py:100-102), so agent i of P that did not leave is agent i - |{leavers l < i}|
+ * of P'.  The leavers are the exit flow's: the cell before the step has an exit among its
+ * neighbours and is not among the positions after it; a step that emptied the env took everybody.
+ * Direction d in [0, NB] (NB = 4 or 8 neighbours): a survivor's is the index of its move in the
+ * reference's neighbour order (Neumann up, down, left, right; Moore row-major), NB for a stay; a
+ * leaver's is the index of the first exit cell among its cell's neighbours.  The origin of an
+ * agent is the cell it was placed on (by ffm_engine_reset, ffm_engine_reset_envs or the
+ * auto-reset; turned on mid-run: the cell it stood on then).
+ * Per class c (class_of_env / n_classes as for the field statistics) the engine keeps, as u64,
+ *   flux[c][cell][NB + 1]     agents that stepped out of `cell` in direction d, or stood still
+ *   present[c][bins]          agents inside before a step, by time since placement
+ *   moved[c][bins]            those of them that moved (leavers move); moved / present is the mean speed
+ *   egress_count[c][cell]     agents placed on `cell` that have left
+ *   egress_steps[c][cell]     the sum of their egress times; egress_steps / egress_count is the mean
+ * After every step launch keyed t, for every env e of it with n0 > 0: tau = t - ep_start_before[e]
+ * in wrapping u32, b = min(tau, bins - 1),
+ *   flux[c][P[i]][d(i)] += 1 for i < n0;  present[c][b] += n0;  moved[c][b] += |{i : d(i) != NB}|;
+ *   for every leaver with origin o:  egress_count[c][o] += 1;  egress_steps[c][o] += tau (not clamped).
+ * A position pair that is no neighbour move (a state the caller made inconsistent) adds nothing
+ * for that agent.  Every sum is an integer: the same bits under any launch geometry, step shards,
+ * the fused-steps setting and either form of the kernel (FFM_MOTION_STATS_FORM=lds|global forces
+ * one and FFM_MOTION_STATS_BLOCKS caps its grid, both read by this call; lds on tables beyond the
+ * LDS budget: FFM_E_INVALID).  The step itself does not change.
+ *
+ * n_classes == 0 turns the feature off and frees everything.  FFM_E_INVALID, the engine exactly as
+ * it was: a negative count, a class outside [0, n_classes), or tables of more than
+ * FFM_MOTION_STATS_MAX_BYTES (one copy: n_classes * (H * W * (NB + 3) + 2 * curve_bins) * 8
+ * bytes).  Philox only (MT: FFM_E_UNSUPPORTED).  Setting it again replaces classes and bins, clears,
+ * and takes the agents' cells at that moment as their origins.
+ *
+ * While on, the engine keeps the exit flow's snapshot (shared with it: it lives while either is
+ * on) and an origin per agent (2 A + 4 bytes per env); ffm_engine_step takes one launch per step (no
+ * fused steps; the state is the same bits) and the motion kernel follows each, before the flow
+ * kernel, on each step shard's own stream where shards are in effect.  ep_start is shared with the
+ * episode log, the field statistics and the exit flow.  Rooms first, the motion statistics after:
+ * ffm_engine_set_env_rooms (on or off) while they are on returns FFM_E_INVALID and leaves the
+ * engine as it was.  Undefined: the affected tau after ffm_engine_set_step_index inside an
+ * episode, and after ffm_engine_set_state the origins of the written envs until their next
+ * placement (flux, present and moved stay defined: the snapshot is refreshed).  Synchronises the
+ * stream. */
+#define FFM_MOTION_STATS_MAX_BYTES FFM_FIELD_STATS_MAX_BYTES
+int ffm_engine_set_motion_stats(ffm_engine* eng, const int32_t* class_of_env, int32_t n_classes, int32_t curve_bins,
+                                void* stream);
+/* flux[C][H * W][NB + 1], present[C][bins], moved[C][bins], egress_count[C][H * W] and
+ * egress_steps[C][H * W] to the host (any may be NULL).  clear != 0 zeroes them afterwards (the
+ * origins stay).  Feature off: FFM_E_INVALID.  Synchronises the stream. */
+int ffm_engine_get_motion_stats(ffm_engine* eng, uint64_t* flux, uint64_t* present, uint64_t* moved,
+                                uint64_t* egress_count, uint64_t* egress_steps, int32_t clear, void* stream);
+
 /* Per-env parameters and agent counts: a whole sweep in one engine.  Replaces the user's loop
  * over FloorFieldModel(params=...) instances, one per point of an evacuation-time-against-N
  * curve (analyze_steps_by_n.py) or of the (k_S, k_D) plane -- each far too small to fill the
